@@ -21,6 +21,10 @@ the MFMA-bound GEMMs of the other); eager2 = that split without the graph.  auto
 SLOWER here (see main()); N > 1 ranks always run eager (the gradient all-reduce is launched from backward callbacks).  The arithmetic is
 the same in all of them; the JSON line says which ran.
 
+--steps K times exactly K steps (`ms_per_step` = their wall time / K).  --dump-outputs DIR then writes what the LAST of them computed: the loss and
+every parameter gradient as DIR/loss.npy and DIR/grad.<parameter>.npy (float32; a gradient of more than 2^18 elements as a fixed, seeded sample:
+dump_outputs()).  Token ids, initial weights and the timed steps' forgetful masks are seeded, so runs with the same arguments see the same inputs.
+
 Extra objects on the JSON line:
   roofline     dominant kernel = the bf16 MFMA NT GEMM on the big tiles (gemm_stag_kernel<NT> 256x256x64 / gemm_kernel<384,256,...,NT>); achieved = algorithmic GEMM FLOPs per launch / average
                launch duration, measured live with HIP events on the launch stream over one instrumented EAGER step; peak = 2500 TFLOP/s.
@@ -33,6 +37,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -45,6 +50,8 @@ import torch  # noqa: E402
 
 B_PER_GPU = 8
 PEAK_BF16_TFLOPS = 2500.0                          # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
+DUMP_SAMPLE = 1 << 18                              # --dump-outputs: elements kept of one gradient (a larger one is sampled)
+DUMP_LIMIT = 64 << 20                              # --dump-outputs: bytes of all files together
 METRIC = 'audio-tokens/sec fwd+bwd, CoarseTransformer d=1024 seq=2048'
 COARSE = dict(dim=1024, depth=6, num_semantic_tokens=500, codebook_size=1024, num_coarse_quantizers=3, flash_attn=True)
 FINE = dict(dim=1024, depth=6, num_coarse_quantizers=3, num_fine_quantizers=5, codebook_size=1024, flash_attn=True)
@@ -68,6 +75,8 @@ def build(config, dev, rank, residual_dtype):
     import audiolm_pytorch_amd as A
     g = torch.Generator().manual_seed(1000 + rank)              # a different synthetic shard per rank
     torch.manual_seed(0)                                        # identical initial weights on every rank
+    random.seed(0)                                              # ... and in every run: each hyper-connection draws its initial residual stream
+                                                                # with Python's random.randrange, like the reference
     B = B_PER_GPU
     if config in ('coarse2048', 'coarse1024', 'e2e_config5'):
         ctor = dict(COARSE)
@@ -159,7 +168,7 @@ def cpu_baseline_and_parity(W, dev, max_seconds=30.0):
     checks the HIP path's loss on EXACTLY that sample (same weights, ids and forgetful mask) against it."""
     import audiolm_pytorch_amd as A
     from audiolm_pytorch_amd import audiolm_pytorch as AP
-    cores = min(os.cpu_count() or 1, 32)          # one GPU's share of the host (256 cores / 8 GPUs); more threads oversubscribe torch's CPU ops
+    cores = min(int(os.environ.get('OMP_NUM_THREADS') or os.cpu_count() or 1), 32)   # one GPU's share of the host (OMP_NUM_THREADS when set); more threads oversubscribe torch's CPU ops
     torch.set_num_threads(cores)
     kind, ctor, model = W['kind'], W['ctor'], W['model']
     sd = {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}
@@ -255,6 +264,32 @@ def pmc_traffic():
     return None, None, 'no PMC summary under profiles/'
 
 
+def dump_outputs(out_dir, loss, named_params, sample=DUMP_SAMPLE):
+    """--dump-outputs: what one timed step hands its caller -- the loss and the parameters' gradients -- as out_dir/loss.npy and
+    out_dir/grad.<parameter name>.npy, float32.  A gradient of more than `sample` elements is written as its flattened elements at the sorted positions
+    torch.randint(numel, (sample,), generator=torch.Generator().manual_seed(zlib.crc32(name))): the same positions in every run and every build.
+    Parameters without a gradient are left out.  -> dict(dir, files, bytes)"""
+    import zlib
+    import numpy as np
+    arrays = {'loss': loss.detach().float().reshape(())}
+    for name, p in named_params:
+        if p.grad is None:
+            continue
+        g = p.grad.detach().reshape(-1)
+        if g.numel() > sample:
+            idx = torch.randint(g.numel(), (sample,), generator=torch.Generator().manual_seed(zlib.crc32(name.encode()))).sort().values
+            g = g[idx.to(g.device)]
+        arrays['grad.' + name] = g.float()
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT} byte limit')
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    return dict(dir=os.path.abspath(out_dir), files=len(arrays), bytes=total)
+
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -273,7 +308,12 @@ def main():
                          'bf16 reduction across ranks -- an explicitly labelled variant (config.dp.bucket_dtype)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-optimizer-leg', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed -- the loss and every parameter gradient -- as DIR/<name>.npy '
+                         '(float32, at most 64 MB; a large gradient as a fixed, seeded sample of its elements), to compare two builds output for output')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -426,8 +466,18 @@ def main():
         loss = step()
     for _ in range(args.warmup):
         loss = step()
-    dt = timed(args.steps, step)
+    last = {}
+
+    def timed_step():
+        last['loss'] = step()
+    # the forgetful masks of the timed steps (one randn draw each) then depend on --steps alone, not on how many steps the priming and the schedule
+    # probe drew: --dump-outputs sees the same inputs in every run with the same arguments
+    torch.manual_seed(0)
+    dt = timed(args.steps, timed_step)
     ms = dt / args.steps * 1e3
+    dumped = None
+    if args.dump_outputs and rank == 0:                        # before any other step overwrites the gradients (or a graph replay the loss)
+        dumped = dump_outputs(args.dump_outputs, last['loss'], model.named_parameters())
     tokens_per_s = world * W['B'] * N / (dt / args.steps)
     dp_stats = None
     if engine is not None:
@@ -755,6 +805,8 @@ def main():
             out['config']['dp'] = dp_stats
         if opt_leg:
             out['with_optimizer'] = opt_leg
+        if dumped:
+            out['dumped_outputs'] = dumped
         if world == 1 and not args.no_cpu_baseline:
             out.update(cpu_baseline_and_parity(W, dev))
             if 'parity' in out:
@@ -769,22 +821,6 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-
-
-def _supervised(cmd, env=None, retries=1):
-    """Runs `cmd` (the measuring process) and, if it is killed by a signal (a core dump at GPU start-up was seen once in a few hundred launches on the
-    shared boxes: same tree, same flags, the next launch ran), runs it again -- at most `retries` times, saying so on stderr.  A Python exception or a
-    failed assertion (ordinary non-zero exit) is never retried.  The child measures itself; nothing about the numbers changes."""
-    import signal
-    import subprocess
-    rc = 0
-    for attempt in range(retries + 1):
-        rc = subprocess.run(cmd, env=env).returncode
-        killed = rc < 0 or rc in (128 + signal.SIGSEGV, 128 + signal.SIGABRT, 128 + signal.SIGBUS)
-        if not killed or attempt == retries:
-            break
-        print(f'[bench.py] measuring process died with {"signal " + str(-rc) if rc < 0 else "exit code " + str(rc)}; running it once more', file=sys.stderr, flush=True)
-    return rc
 
 
 def _requested_gpus(argv):
@@ -808,7 +844,6 @@ def _self_launch(ngpus):
         s.bind(('127.0.0.1', 0))
         port = s.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0'))   # dmabuf IPC: RCCL needs it on these hosts
-    env.pop('ALM_BENCH_CHILD', None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={ngpus}', '--master-addr', '127.0.0.1', '--master-port', str(port),
            os.path.abspath(__file__), *sys.argv[1:]]
     print(f'[bench.py] --gpus {ngpus} without WORLD_SIZE: launching {ngpus} ranks myself: {" ".join(cmd[1:8])} bench.py ...', file=sys.stderr, flush=True)
@@ -818,15 +853,11 @@ def _self_launch(ngpus):
 if __name__ == '__main__':
     import faulthandler
     faulthandler.enable()                 # a SIGSEGV / SIGABRT inside a native call prints the Python stack of every thread: WHICH launch died
-    # single-process runs are measured in a child process that is re-launched once if it is killed by a signal; under torch.distributed.run
-    # (one rank per GPU, rendezvous owned by the launcher) every rank measures in place; `--gpus N` typed without a launcher starts one itself
+    # a single process and every rank under torch.distributed.run (one rank per GPU, rendezvous owned by the launcher) measure in place; `--gpus N`
+    # typed without a launcher starts one itself.  A measuring process that dies is never started again: its failure is the result.
     _world_env = int(os.environ.get('WORLD_SIZE', '1'))
     _want = _requested_gpus(sys.argv[1:])
     if _want > 1 and _world_env == 1 and 'RANK' not in os.environ:
         rc = _self_launch(_want)
         sys.exit(rc if rc >= 0 else 128 - rc)
-    if os.environ.get('ALM_BENCH_CHILD') == '1' or _world_env > 1 or os.environ.get('ALM_BENCH_SUPERVISE', '1') == '0':
-        main()
-    else:
-        rc = _supervised([sys.executable, os.path.abspath(__file__), *sys.argv[1:]], env=dict(os.environ, ALM_BENCH_CHILD='1'))
-        sys.exit(rc if rc >= 0 else 128 - rc)
+    main()

@@ -131,7 +131,7 @@ def test_full_size_matches_oracle(kind, streams, N_kind, residual, batch):
     orig_synth = TG.synth_state_dict
     TG.synth_state_dict = lambda shapes_, seed_: {k: v.clone() for k, v in state.items()}      # oracle_run() re-synthesises from (shapes, seed)
 
-    torch.set_num_threads(min(os.cpu_count() or 1, 32))
+    torch.set_num_threads(min(int(os.environ.get('OMP_NUM_THREADS') or os.cpu_count() or 1), 32))     # the process's CPU share when the host sets one
     t0 = time.time()
     oloss, ologits, ograds = oracle_run(fx)                                   # fp32 CPU oracle, same synthetic parameters (shapes, seed)
     t_oracle = time.time() - t0
