@@ -8,10 +8,10 @@ configs[1]/[3]).
 One process per GPU; per-rank batch B = 8 (weak scaling); a "step" = CoarseTransformerWrapper.forward(return_loss=True) +
 backward (+ RCCL gradient all-reduce over xGMI for N > 1), inputs resident in HBM, the bf16 weight copies are re-packed from
 the fp32 masters every step (as after an optimiser step).  The optimiser itself is outside the metric ("fwd+bwd"); a second
-timed loop that includes the clip + Adam step is reported as `with_optimizer` for reference.
+timed loop that includes the clip + Adam step is reported as `with_optimizer` for reference (--full).
 
---config selects the other BASELINE.json configurations / SURVEY §8(d) rows (same JSON contract, each with its own roofline and CPU
-baseline): coarse2048 (default, the metric's configuration), coarse1024 (configs[1]), fine2049 (configs[2]), fine_t2048_q8 (the other
+--config selects the other BASELINE.json configurations / SURVEY §8(d) rows (same JSON contract; with --full each with its own roofline and
+CPU baseline): coarse2048 (default, the metric's configuration), coarse1024 (configs[1]), fine2049 (configs[2]), fine_t2048_q8 (the other
 reading of "(B=8, Q=8, seq=2048)": a 2048-frame x 8-quantizer grid, N = 16385), e2e_config5 (configs[4]: SoundStream tokenize of
 8 x 30 s @ 24 kHz + CoarseTransformer codebook 4096, N = 8253).
 
@@ -25,7 +25,12 @@ the same in all of them; the JSON line says which ran.
 every parameter gradient as DIR/loss.npy and DIR/grad.<parameter>.npy (float32; a gradient of more than 2^18 elements as a fixed, seeded sample:
 dump_outputs()).  Token ids, initial weights and the timed steps' forgetful masks are seeded, so runs with the same arguments see the same inputs.
 
-Extra objects on the JSON line:
+A plain run does only what the headline figure needs: set up (the `auto` schedule probe included: it decides what the timed steps run), prime,
+warm up, time the K steps, --dump-outputs, print the JSON line.  --full adds the measurements that take steps or runs of their own, after the
+timed region: host issue time per step, the instrumented roofline step, the optimiser leg and, at N = 1, the CPU baseline + loss parity (exit
+code 3 when that parity fails); --no-cpu-baseline / --no-optimizer-leg leave out those two legs of a --full run.
+
+Extra objects on the JSON line with --full:
   roofline     dominant kernel = the bf16 MFMA NT GEMM on the big tiles (gemm_stag_kernel<NT> 256x256x64 / gemm_kernel<384,256,...,NT>); achieved = algorithmic GEMM FLOPs per launch / average
                launch duration, measured live with HIP events on the launch stream over one instrumented EAGER step; peak = 2500 TFLOP/s.
   cpu_baseline the oracle (CPU fp32 restatement of the reference, "port") timed on this box's host cores on a bounded sample
@@ -290,233 +295,16 @@ def dump_outputs(out_dir, loss, named_params, sample=DUMP_SAMPLE):
     return dict(dir=os.path.abspath(out_dir), files=len(arrays), bytes=total)
 
 
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--config', default='coarse2048', choices=['coarse2048', 'coarse1024', 'fine2049', 'fine_t2048_q8', 'e2e_config5'])
-    ap.add_argument('--schedule', default='auto', choices=['auto', 'eager', 'eager2', 'graph', 'graph2'])
-    ap.add_argument('--residual', default='auto', choices=['auto', 'bf16', 'fp32'],
-                    help='HBM storage of the 4 hyper-connection residual streams.  auto (default) = the SHIPPED default: the model is built without '
-                         'residual_dtype and the forward runs inside torch.autocast(bfloat16) like reference trainer.py:1241 -> bf16 streams (what autocast '
-                         'gives the reference); bf16 / fp32 = built with that storage explicitly, no autocast context')
-    ap.add_argument('--bucket-dtype', default='auto', choices=['auto', 'bf16', 'fp32'],
-                    help='wire format of the gradient all-reduce buckets for N > 1.  auto = fp32: what the reference reduces (DDP / accelerate all-reduce fp32 '
-                         'gradients), so the scaling numbers are like for like; bf16 halves the bytes on the xGMI ring (131 instead of 262 MB/step) at the price of a '
-                         'bf16 reduction across ranks -- an explicitly labelled variant (config.dp.bucket_dtype)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-optimizer-leg', action='store_true')
-    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
-                    help='after the timed steps, write what the last timed step computed -- the loss and every parameter gradient -- as DIR/<name>.npy '
-                         '(float32, at most 64 MB; a large gradient as a fixed, seeded sample of its elements), to compare two builds output for output')
-    args = ap.parse_args()
-    if args.steps < 1 or args.warmup < 0:
-        ap.error('--steps must be >= 1 and --warmup >= 0')
-
-    world = int(os.environ.get('WORLD_SIZE', '1'))
-    rank = int(os.environ.get('RANK', '0'))
-    local_rank = int(os.environ.get('LOCAL_RANK', '0'))
-    if os.environ.get('ALM_BENCH_LAUNCH_CHECK') == '1':
-        # launcher self-test (tests/test_bench_launch.py, runs without a GPU): every rank joins a gloo group, one all-reduce proves the rendezvous the
-        # self-launch set up works, rank 0 prints ONE JSON line.  Nothing is measured.
-        import datetime
-        import torch.distributed as dist
-        assert world == args.gpus, (world, args.gpus)
-        if world > 1:
-            dist.init_process_group('gloo', timeout=datetime.timedelta(seconds=120))
-            t = torch.ones(1)
-            dist.all_reduce(t)
-            assert int(t) == world
-            dist.barrier()
-            dist.destroy_process_group()
-        if rank == 0:
-            print(json.dumps({'launch_check': True, 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup}), flush=True)
-        return
-    assert torch.cuda.is_available(), 'bench.py needs MI355X GPUs'
-    # test hook (scripts/gpu_check.sh dp2): ALM_BENCH_SHARE_GPU=1 runs every rank on cuda:0 over gloo, to exercise the multi-rank control flow
-    # (callbacks, bucket order, barriers) on a 1-GPU box; its numbers mean nothing
-    share = os.environ.get('ALM_BENCH_SHARE_GPU') == '1'
-    if share:
-        local_rank = 0
-    torch.cuda.set_device(local_rank)
-    dev = torch.device('cuda', local_rank)
-    dist = None
-    if world > 1:
-        import datetime
-        import torch.distributed as dist
-        print(f'[bench rank {rank}/{world}] init_process_group on cuda:{local_rank}', file=sys.stderr, flush=True)
-        if share:
-            dist.init_process_group('gloo', timeout=datetime.timedelta(seconds=300))
-        else:
-            dist.init_process_group('nccl', device_id=dev, timeout=datetime.timedelta(seconds=300))      # backend "nccl" IS RCCL on ROCm
-    assert world == args.gpus, f'--gpus {args.gpus} but WORLD_SIZE={world}: the launcher started {world} ranks (python bench.py --gpus N starts its own N ranks when no launcher did)'
-
-    from audiolm_pytorch_amd import core, graphed, launchlist, ops, parallel
-    import audiolm_pytorch_amd as A
-
-    W = build(args.config, dev, rank, {'bf16': torch.bfloat16, 'fp32': torch.float32, 'auto': None}[args.residual])
-    # --residual auto: the training call runs under autocast exactly as trainer.py:1241 (`with self.accelerator.autocast(): loss = train_wrapper(...)`);
-    # it changes nothing in the HIP launches (they take raw pointers) except that the default-constructed model then stores bf16 residual streams
-    import contextlib
-    amp = (lambda: torch.autocast('cuda', dtype=torch.bfloat16)) if args.residual == 'auto' else contextlib.nullcontext
-    W['amp'] = amp
-    model, wrapper, inputs, N = W['model'], W['wrapper'], W['inputs'], W['N']
-    bucket_dtype = torch.bfloat16 if args.bucket_dtype == 'bf16' else torch.float32
-    engine = parallel.DataParallelEngine(model, dist, bucket_dtype=bucket_dtype) if world > 1 else None
-    cache = model.transformer._cache
-    params = list(model.parameters())                           # (as optimizer.zero_grad(set_to_none=True) holds them: no module-tree walk per step)
-
-    def eager_step(opt=None, repack=True):
-        if repack:
-            cache.store.clear()                                 # weights "changed": re-pack bf16 copies like after an optimiser step
-        for p in params:
-            p.grad = None
-        with amp():
-            loss = wrapper(**inputs, return_loss=True)
-        loss.backward()
-        if engine is not None:
-            engine.finish()                                     # waits for the overlapped RCCL all-reduces, grads averaged in place
-        if opt is not None:
-            opt.step()
-        return loss.detach()
-
-    def barrier():
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    # ---- schedule
-    schedule, note, gstep = 'eager', None, None
-    want = args.schedule
-    probe = None
-    auto = want == 'auto'
-    if auto:
-        # measured on MI355X (profiles/r2_schedules.log) at the headline shape: eager 15.5 ms, graph 16.2 ms, graph2 17.1 ms per step -- there the
-        # GPU, not the host, is the limit (host issue ~11 ms < 14 ms) and a replayed graph only adds a per-node gap to ~900 kernels.  The smaller
-        # configurations are the other way round (coarse1024: 8.4 ms of GPU work against 8-9 ms of host issue), so `auto` PROBES: a few eager steps
-        # and a few replays of the captured step, and the timed region below runs whichever was faster (both probe figures are reported).
-        want = 'eager'
-    if want == 'eager2':                                        # diagnostic: the two-half-batch schedule without a graph (host-bound)
-        model.transformer.micro_batches = 2
-        schedule = 'eager2'
-    for _ in range(3):                                          # lazy initialisation before any capture
-        eager_step()
-    if want in ('graph', 'graph2') and world == 1:
-        try:
-            with amp():
-                gstep = graphed.GraphedTrainStep(wrapper, inputs, micro_batches=2 if want == 'graph2' else 1)
-            torch.cuda.synchronize()
-            schedule = want
-        except Exception as e:                                  # capture is an optimisation: report why it was not used, run eager
-            note = f'{want} capture failed ({type(e).__name__}: {str(e)[:160]}); ran eager'
-            print('[bench] ' + note, file=sys.stderr, flush=True)
-            gstep = None
-            torch.cuda.synchronize()
-    elif want not in ('eager', 'eager2'):
-        note = f'{want} is a single-GPU schedule (the gradient all-reduce is issued from backward callbacks); ran eager'
-
-    def step(opt=None, repack=True):
-        if gstep is not None:
-            loss = gstep(**inputs)
-            if opt is not None:
-                opt.step()
-            return loss
-        return eager_step(opt, repack)
-
-    def timed(nsteps, fn):
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(nsteps):
-            fn()
-        barrier()
-        dt = time.perf_counter() - t0
-        if dist is not None:
-            t = torch.tensor([dt], device=dev, dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt = float(t)
-        return dt
-
-    if auto and world == 1 and N <= 4096:
-        for _ in range(8):
-            eager_step()
-        te = timed(6, eager_step) / 6 * 1e3
-        probe = {'eager_ms': round(te, 3)}
-        try:
-            with amp():
-                cand = graphed.GraphedTrainStep(wrapper, inputs, micro_batches=1)
-            torch.cuda.synchronize()
-            for _ in range(3):
-                cand(**inputs)
-            tg = timed(6, lambda: cand(**inputs)) / 6 * 1e3
-            probe['graph_ms'] = round(tg, 3)
-            if tg < 0.97 * te:                                  # a clear win only: the eager path keeps the weight-gradient side stream
-                gstep, schedule = cand, 'graph'
-            else:
-                del cand
-        except Exception as e:
-            probe['graph_error'] = f'{type(e).__name__}: {str(e)[:120]}'
-            torch.cuda.synchronize()
-
-    # untimed priming in addition to --warmup: the first steps grow the caching allocator's pools (main + side stream) and run at ramping
-    # clocks; measured on MI355X the step time only settles after ~10 steps (17.6 -> 16.4 ms).  The timed region below is exactly --steps steps.
-    big = N > 4096
-    for _ in range(3 if big else 10):
-        loss = step()
-    for _ in range(args.warmup):
-        loss = step()
-    last = {}
-
-    def timed_step():
-        last['loss'] = step()
-    # the forgetful masks of the timed steps (one randn draw each) then depend on --steps alone, not on how many steps the priming and the schedule
-    # probe drew: --dump-outputs sees the same inputs in every run with the same arguments
-    torch.manual_seed(0)
-    dt = timed(args.steps, timed_step)
-    ms = dt / args.steps * 1e3
-    dumped = None
-    if args.dump_outputs and rank == 0:                        # before any other step overwrites the gradients (or a graph replay the loss)
-        dumped = dump_outputs(args.dump_outputs, last['loss'], model.named_parameters())
-    tokens_per_s = world * W['B'] * N / (dt / args.steps)
-    dp_stats = None
-    if engine is not None:
-        # one line per rank on stderr, so that a driver SCALE run is diagnosable from its tail: what went on the wire and how much of the exchange
-        # did NOT hide under backward (host time from the launch of the last bucket to the return of finish())
-        dp_stats = dict(engine.last_stats or {}, bucket_dtype=str(bucket_dtype).replace('torch.', ''), ms_per_step=round(ms, 3))
-        # GPU-clock time of the LAST step between "backward's own kernels done" and "every bucket reduced and handed out": the part of the gradient
-        # exchange that did not hide under backward (events recorded in finish(); read here, outside the timed region)
-        dp_stats['exposed_tail_ms'] = engine.exposed_tail_ms()
-        print(f'[bench rank {rank}/{world}] dp: {dp_stats["buckets"]} buckets, {dp_stats["bytes"] / 1e6:.1f} MB/step on the wire ({dp_stats["bucket_dtype"]}), '
-              f'{dp_stats.get("direct_buckets", 0)} of them reduced in place, exposed tail {dp_stats["exposed_tail_ms"]} ms on the GPU clock (host: {dp_stats["tail_ms"]} ms after the last bucket launch), step {ms:.3f} ms, collectives issued from a side stream: '
-              f'{any(sid != int(torch.cuda.current_stream(dev).cuda_stream) for sid in dp_stats.get("launch_streams", []))}', file=sys.stderr, flush=True)
-
-    # host time to ISSUE one step (no synchronisation inside): eager launches vs one graph replay
-    host = {}
-    issue = []
-    for _ in range(5):                                          # median of 5 single steps (one sample swings by +-1.5 ms with the host's other work)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        eager_step()
-        issue.append((time.perf_counter() - t0) * 1e3)
-    host['eager_issue_ms'] = round(sorted(issue)[2], 3)
-    host['eager_issue_ms_samples'] = [round(v, 3) for v in issue]
-    host['launch_list'] = dict(launchlist.STATS, enabled=launchlist.ENABLED)       # stack passes sized / recorded / replayed so far (replayed > 0: the timed steps ran from the lists)
-    torch.cuda.synchronize()
-    if gstep is not None:
-        t0 = time.perf_counter()
-        gstep(**inputs)
-        host['graph_replay_issue_ms'] = round((time.perf_counter() - t0) * 1e3, 3)
-        torch.cuda.synchronize()
-        dte = timed(max(3, args.steps // 2), eager_step)
-        host['eager_ms_per_step'] = round(dte / max(3, args.steps // 2) * 1e3, 3)
-
+def roofline(W, config, eager_step, tokens_per_s, world):
+    """--full: the JSON line's `roofline` object (None when the step ran no big-tile NT GEMM)"""
     # ---- roofline of the dominant kernel: one instrumented EAGER step, HIP events (torch.cuda.Event on the launch stream = torch's current
     # stream, which is the stream every alm_* launch uses) around every MFMA GEMM launch.  The dominant kernel is the NT big-tile GEMM (8 waves: gemm_stag_kernel
     # <false,*> 256x256x64 with staggered wave rows, or gemm_kernel<384,256,2,4,false,*> where pick_tile() prefers the coarser tiling): its
     # launches are singled out; all GEMM launches are reported alongside.
     # EVERY rank runs the instrumented step (with N > 1 it contains the gradient all-reduces: a step on rank 0 alone would dead-lock the
     # collectives); only rank 0's numbers are reported.
+    from audiolm_pytorch_amd import core, launchlist, ops
+    N = W['N']
     roof = None
     events = []                                                  # (start event, end event, algorithmic work, unit, kernel key)
     timed_names = ('gemm_nt', 'gemm_nt_group2', 'gemm_tn_splitk', 'gemm_tn_batched', 'mqa_attn_fwd', 'mqa_attn_bwd', 'hc_fwd', 'hc_bwd', 'geglu_ln_fwd', 'geglu_ln_bwd', 'layernorm_fwd',
@@ -680,8 +468,8 @@ def main():
         traffic, traffic_src, traffic_note = pmc_traffic()
         roof = {'bound': 'mfma', 'kernel': 'gemm_stag_kernel<NT> 256x256x64 + gemm_kernel<384,256,2,4,NT> (8-wave bf16 MFMA 32x32x16 big tiles; FFN / projection forward + dgrad GEMMs)',
                 'achieved': round(ach, 1), 'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s', 'frac': round(ach / PEAK_BF16_TFLOPS, 4),
-                'traffic': traffic if args.config == 'coarse2048' else None,
-                'traffic_source': traffic_note if args.config == 'coarse2048' else None,
+                'traffic': traffic if config == 'coarse2048' else None,
+                'traffic_source': traffic_note if config == 'coarse2048' else None,
                 'launches_per_step': d_n, 'avg_launch_us': round(d_ms * 1e3 / d_n, 2),
                 'flop_per_launch_avg': round(d_fl / d_n, 0),
                 'measured_in': 'one instrumented eager step, weight-gradient side stream off (kernels do not overlap); HIP events on the launch stream bracket each '
@@ -691,11 +479,248 @@ def main():
                 'kernels': kernels,
                 'instrumented_ms_per_step': round(sum(v[0] for v in agg.values()), 3),
                 'model_flops_frac': round(tokens_per_s / world * flops_per_token(W['kind'], N, W['ctor'].get('codebook_size', 1024)) / (PEAK_BF16_TFLOPS * 1e12), 4)}
-    if dist is not None:
-        dist.barrier()
+    return roof
+
+
+def arg_parser():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--gpus', type=int, default=1)
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--config', default='coarse2048', choices=['coarse2048', 'coarse1024', 'fine2049', 'fine_t2048_q8', 'e2e_config5'])
+    ap.add_argument('--schedule', default='auto', choices=['auto', 'eager', 'eager2', 'graph', 'graph2'])
+    ap.add_argument('--residual', default='auto', choices=['auto', 'bf16', 'fp32'],
+                    help='HBM storage of the 4 hyper-connection residual streams.  auto (default) = the SHIPPED default: the model is built without '
+                         'residual_dtype and the forward runs inside torch.autocast(bfloat16) like reference trainer.py:1241 -> bf16 streams (what autocast '
+                         'gives the reference); bf16 / fp32 = built with that storage explicitly, no autocast context')
+    ap.add_argument('--bucket-dtype', default='auto', choices=['auto', 'bf16', 'fp32'],
+                    help='wire format of the gradient all-reduce buckets for N > 1.  auto = fp32: what the reference reduces (DDP / accelerate all-reduce fp32 '
+                         'gradients), so the scaling numbers are like for like; bf16 halves the bytes on the xGMI ring (131 instead of 262 MB/step) at the price of a '
+                         'bf16 reduction across ranks -- an explicitly labelled variant (config.dp.bucket_dtype)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what the headline figure does not need: host issue time, the instrumented roofline step, '
+                         'the optimiser leg and (N = 1) the CPU baseline + loss parity')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline + loss parity')
+    ap.add_argument('--no-optimizer-leg', action='store_true', help='--full without the optimiser leg')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed -- the loss and every parameter gradient -- as DIR/<name>.npy '
+                         '(float32, at most 64 MB; a large gradient as a fixed, seeded sample of its elements), to compare two builds output for output')
+    return ap
+
+
+def main():
+    ap = arg_parser()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if (args.no_cpu_baseline or args.no_optimizer_leg) and not args.full:
+        print('[bench] --no-cpu-baseline / --no-optimizer-leg trim a --full run; a plain run has neither leg', file=sys.stderr, flush=True)
+
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    rank = int(os.environ.get('RANK', '0'))
+    local_rank = int(os.environ.get('LOCAL_RANK', '0'))
+    if os.environ.get('ALM_BENCH_LAUNCH_CHECK') == '1':
+        # launcher self-test (tests/test_bench_launch.py, runs without a GPU): every rank joins a gloo group, one all-reduce proves the rendezvous the
+        # self-launch set up works, rank 0 prints ONE JSON line.  Nothing is measured.
+        import datetime
+        import torch.distributed as dist
+        assert world == args.gpus, (world, args.gpus)
+        if world > 1:
+            dist.init_process_group('gloo', timeout=datetime.timedelta(seconds=120))
+            t = torch.ones(1)
+            dist.all_reduce(t)
+            assert int(t) == world
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps({'launch_check': True, 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup}), flush=True)
+        return
+    assert torch.cuda.is_available(), 'bench.py needs MI355X GPUs'
+    # test hook (scripts/gpu_check.sh dp2): ALM_BENCH_SHARE_GPU=1 runs every rank on cuda:0 over gloo, to exercise the multi-rank control flow
+    # (callbacks, bucket order, barriers) on a 1-GPU box; its numbers mean nothing
+    share = os.environ.get('ALM_BENCH_SHARE_GPU') == '1'
+    if share:
+        local_rank = 0
+    torch.cuda.set_device(local_rank)
+    dev = torch.device('cuda', local_rank)
+    dist = None
+    if world > 1:
+        import datetime
+        import torch.distributed as dist
+        print(f'[bench rank {rank}/{world}] init_process_group on cuda:{local_rank}', file=sys.stderr, flush=True)
+        if share:
+            dist.init_process_group('gloo', timeout=datetime.timedelta(seconds=300))
+        else:
+            dist.init_process_group('nccl', device_id=dev, timeout=datetime.timedelta(seconds=300))      # backend "nccl" IS RCCL on ROCm
+    assert world == args.gpus, f'--gpus {args.gpus} but WORLD_SIZE={world}: the launcher started {world} ranks (python bench.py --gpus N starts its own N ranks when no launcher did)'
+
+    from audiolm_pytorch_amd import core, graphed, launchlist, parallel
+    import audiolm_pytorch_amd as A
+
+    W = build(args.config, dev, rank, {'bf16': torch.bfloat16, 'fp32': torch.float32, 'auto': None}[args.residual])
+    # --residual auto: the training call runs under autocast exactly as trainer.py:1241 (`with self.accelerator.autocast(): loss = train_wrapper(...)`);
+    # it changes nothing in the HIP launches (they take raw pointers) except that the default-constructed model then stores bf16 residual streams
+    import contextlib
+    amp = (lambda: torch.autocast('cuda', dtype=torch.bfloat16)) if args.residual == 'auto' else contextlib.nullcontext
+    W['amp'] = amp
+    model, wrapper, inputs, N = W['model'], W['wrapper'], W['inputs'], W['N']
+    bucket_dtype = torch.bfloat16 if args.bucket_dtype == 'bf16' else torch.float32
+    engine = parallel.DataParallelEngine(model, dist, bucket_dtype=bucket_dtype) if world > 1 else None
+    cache = model.transformer._cache
+    params = list(model.parameters())                           # (as optimizer.zero_grad(set_to_none=True) holds them: no module-tree walk per step)
+
+    def eager_step(opt=None, repack=True):
+        if repack:
+            cache.store.clear()                                 # weights "changed": re-pack bf16 copies like after an optimiser step
+        for p in params:
+            p.grad = None
+        with amp():
+            loss = wrapper(**inputs, return_loss=True)
+        loss.backward()
+        if engine is not None:
+            engine.finish()                                     # waits for the overlapped RCCL all-reduces, grads averaged in place
+        if opt is not None:
+            opt.step()
+        return loss.detach()
+
+    def barrier():
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    # ---- schedule
+    schedule, note, gstep = 'eager', None, None
+    want = args.schedule
+    probe = None
+    auto = want == 'auto'
+    if auto:
+        # measured on MI355X (profiles/r2_schedules.log) at the headline shape: eager 15.5 ms, graph 16.2 ms, graph2 17.1 ms per step -- there the
+        # GPU, not the host, is the limit (host issue ~11 ms < 14 ms) and a replayed graph only adds a per-node gap to ~900 kernels.  The smaller
+        # configurations are the other way round (coarse1024: 8.4 ms of GPU work against 8-9 ms of host issue), so `auto` PROBES: a few eager steps
+        # and a few replays of the captured step, and the timed region below runs whichever was faster (both probe figures are reported).
+        want = 'eager'
+    if want == 'eager2':                                        # diagnostic: the two-half-batch schedule without a graph (host-bound)
+        model.transformer.micro_batches = 2
+        schedule = 'eager2'
+    for _ in range(3):                                          # lazy initialisation before any capture
+        eager_step()
+    if want in ('graph', 'graph2') and world == 1:
+        try:
+            with amp():
+                gstep = graphed.GraphedTrainStep(wrapper, inputs, micro_batches=2 if want == 'graph2' else 1)
+            torch.cuda.synchronize()
+            schedule = want
+        except Exception as e:                                  # capture is an optimisation: report why it was not used, run eager
+            note = f'{want} capture failed ({type(e).__name__}: {str(e)[:160]}); ran eager'
+            print('[bench] ' + note, file=sys.stderr, flush=True)
+            gstep = None
+            torch.cuda.synchronize()
+    elif want not in ('eager', 'eager2'):
+        note = f'{want} is a single-GPU schedule (the gradient all-reduce is issued from backward callbacks); ran eager'
+
+    def step(opt=None, repack=True):
+        if gstep is not None:
+            loss = gstep(**inputs)
+            if opt is not None:
+                opt.step()
+            return loss
+        return eager_step(opt, repack)
+
+    def timed(nsteps, fn):
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(nsteps):
+            fn()
+        barrier()
+        dt = time.perf_counter() - t0
+        if dist is not None:
+            t = torch.tensor([dt], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t)
+        return dt
+
+    if auto and world == 1 and N <= 4096:
+        for _ in range(8):
+            eager_step()
+        te = timed(6, eager_step) / 6 * 1e3
+        probe = {'eager_ms': round(te, 3)}
+        try:
+            with amp():
+                cand = graphed.GraphedTrainStep(wrapper, inputs, micro_batches=1)
+            torch.cuda.synchronize()
+            for _ in range(3):
+                cand(**inputs)
+            tg = timed(6, lambda: cand(**inputs)) / 6 * 1e3
+            probe['graph_ms'] = round(tg, 3)
+            if tg < 0.97 * te:                                  # a clear win only: the eager path keeps the weight-gradient side stream
+                gstep, schedule = cand, 'graph'
+            else:
+                del cand
+        except Exception as e:
+            probe['graph_error'] = f'{type(e).__name__}: {str(e)[:120]}'
+            torch.cuda.synchronize()
+
+    # untimed priming in addition to --warmup: the first steps grow the caching allocator's pools (main + side stream) and run at ramping
+    # clocks; measured on MI355X the step time only settles after ~10 steps (17.6 -> 16.4 ms).  The timed region below is exactly --steps steps.
+    big = N > 4096
+    for _ in range(3 if big else 10):
+        loss = step()
+    for _ in range(args.warmup):
+        loss = step()
+    last = {}
+
+    def timed_step():
+        last['loss'] = step()
+    # the forgetful masks of the timed steps (one randn draw each) then depend on --steps alone, not on how many steps the priming and the schedule
+    # probe drew: --dump-outputs sees the same inputs in every run with the same arguments
+    torch.manual_seed(0)
+    dt = timed(args.steps, timed_step)
+    ms = dt / args.steps * 1e3
+    dumped = None
+    if args.dump_outputs and rank == 0:                        # before any other step overwrites the gradients (or a graph replay the loss)
+        dumped = dump_outputs(args.dump_outputs, last['loss'], model.named_parameters())
+    tokens_per_s = world * W['B'] * N / (dt / args.steps)
+    dp_stats = None
+    if engine is not None:
+        # one line per rank on stderr, so that a driver SCALE run is diagnosable from its tail: what went on the wire and how much of the exchange
+        # did NOT hide under backward (host time from the launch of the last bucket to the return of finish())
+        dp_stats = dict(engine.last_stats or {}, bucket_dtype=str(bucket_dtype).replace('torch.', ''), ms_per_step=round(ms, 3))
+        # GPU-clock time of the LAST step between "backward's own kernels done" and "every bucket reduced and handed out": the part of the gradient
+        # exchange that did not hide under backward (events recorded in finish(); read here, outside the timed region)
+        dp_stats['exposed_tail_ms'] = engine.exposed_tail_ms()
+        print(f'[bench rank {rank}/{world}] dp: {dp_stats["buckets"]} buckets, {dp_stats["bytes"] / 1e6:.1f} MB/step on the wire ({dp_stats["bucket_dtype"]}), '
+              f'{dp_stats.get("direct_buckets", 0)} of them reduced in place, exposed tail {dp_stats["exposed_tail_ms"]} ms on the GPU clock (host: {dp_stats["tail_ms"]} ms after the last bucket launch), step {ms:.3f} ms, collectives issued from a side stream: '
+              f'{any(sid != int(torch.cuda.current_stream(dev).cuda_stream) for sid in dp_stats.get("launch_streams", []))}', file=sys.stderr, flush=True)
+
+    # --full: host time to ISSUE one step (no synchronisation inside): eager launches vs one graph replay
+    host = {}
+    if args.full:
+        issue = []
+        for _ in range(5):                                      # median of 5 single steps (one sample swings by +-1.5 ms with the host's other work)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eager_step()
+            issue.append((time.perf_counter() - t0) * 1e3)
+        host['eager_issue_ms'] = round(sorted(issue)[2], 3)
+        host['eager_issue_ms_samples'] = [round(v, 3) for v in issue]
+    host['launch_list'] = dict(launchlist.STATS, enabled=launchlist.ENABLED)       # stack passes sized / recorded / replayed so far (replayed > 0: the timed steps ran from the lists)
+    torch.cuda.synchronize()
+    if args.full and gstep is not None:
+        t0 = time.perf_counter()
+        gstep(**inputs)
+        host['graph_replay_issue_ms'] = round((time.perf_counter() - t0) * 1e3, 3)
+        torch.cuda.synchronize()
+        dte = timed(max(3, args.steps // 2), eager_step)
+        host['eager_ms_per_step'] = round(dte / max(3, args.steps // 2) * 1e3, 3)
+
+    roof = None
+    if args.full:
+        roof = roofline(W, args.config, eager_step, tokens_per_s, world)
+        if dist is not None:
+            dist.barrier()
 
     opt_leg = None
-    if not args.no_optimizer_leg:
+    if args.full and not args.no_optimizer_leg:
         # full training step as the reference trainer runs it (trainer.py:1241-1255): fwd + bwd (+ gradient all-reduce) + clip_grad_norm_(0.5)
         # + Adam (optimizer.py:get_optimizer, wd = 0 -> Adam).  Ours: FusedAdam (two HIP launches, norm kept on the device); beside it the
         # same step with torch.optim.Adam + torch.nn.utils.clip_grad_norm_ as the stock baseline.
@@ -807,7 +832,7 @@ def main():
             out['with_optimizer'] = opt_leg
         if dumped:
             out['dumped_outputs'] = dumped
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out.update(cpu_baseline_and_parity(W, dev))
             if 'parity' in out:
                 out['config']['parity_sample_N'] = out['parity']['sample_N']    # the sequence length the in-bench loss parity check ran at (== seq_len unless stated)

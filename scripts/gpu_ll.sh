@@ -16,7 +16,7 @@ for r in 1 2; do
   for ll in 1 0; do
     for cfg in coarse2048 coarse1024; do
       echo "== bench $cfg ALM_LAUNCH_LIST=$ll round $r"
-      ALM_LAUNCH_LIST=$ll timeout 600 python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-optimizer-leg 2>/dev/null | python -c "
+      ALM_LAUNCH_LIST=$ll timeout 600 python bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-optimizer-leg 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

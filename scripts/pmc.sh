@@ -1,17 +1,18 @@
 #!/bin/bash
 # PMC passes (one counter group per run, kernel-trace only -- never combined with sys/hip traces) over a short bench.py run.
-# usage: scripts/pmc.sh "<counters>" <tag>     -> gpurun_out/pmc_<tag>.csv (per-kernel averages)
+# usage: scripts/pmc.sh "<counters>" <tag>     -> $LOG_DIR/pmc_<tag>.csv (per-kernel averages)
 cnt="$1"; tag="$2"
-mkdir -p gpurun_out
+export LOG_DIR=${LOG_DIR:-gpu_logs}
+mkdir -p $LOG_DIR
 export TMPDIR=/tmp
 export ALM_BENCH_SUPERVISE=0      # profilers follow ONE process: bench.py measures in place (no re-launching child)
 d=/tmp/pmc_$tag
 rm -rf $d
-timeout 600 rocprofv3 --pmc $cnt --kernel-trace --output-format csv -d $d -o p -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-optimizer-leg > gpurun_out/pmc_$tag.log 2>&1
+timeout 600 rocprofv3 --pmc $cnt --kernel-trace --output-format csv -d $d -o p -- python bench.py --steps 2 --warmup 1 > $LOG_DIR/pmc_$tag.log 2>&1
 echo "rc=$?"
 f=$(find $d -name "*counter_collection.csv" | head -1)
 echo "file: $f"
-python - "$f" gpurun_out/pmc_$tag.csv <<'PY'
+python - "$f" $LOG_DIR/pmc_$tag.csv <<'PY'
 import csv, sys, collections
 src, out = sys.argv[1], sys.argv[2]
 agg = collections.defaultdict(lambda: collections.defaultdict(lambda: [0.0, 0]))

@@ -1,5 +1,5 @@
 """bench.py --dump-outputs (CPU): the files dump_outputs() writes for the last timed step -- loss + parameter gradients, float32, a large gradient as a
-fixed seeded sample, never more than the byte limit -- and the argument checks of --steps / --dump-outputs."""
+fixed seeded sample, never more than the byte limit -- and the argument checks of --steps / --dump-outputs / --full."""
 import importlib.util
 import os
 import subprocess
@@ -70,6 +70,19 @@ def test_steps_must_be_positive_and_dump_outputs_is_accepted(tmp_path):
     r = _run(['--steps', '3', '--warmup', '0', '--dump-outputs', str(tmp_path / 'out')])
     assert r.returncode == 0, r.stderr[-2000:]
     assert '"steps": 3' in r.stdout
+
+
+def test_full_is_off_by_default():
+    """a plain run measures the headline figure alone; the host-issue, roofline, optimiser and CPU-baseline legs run with --full"""
+    ap = _bench().arg_parser()
+    plain = ap.parse_args(['--gpus', '1', '--steps', '4', '--warmup', '2'])
+    assert not plain.full
+    full = ap.parse_args(['--full', '--no-cpu-baseline'])
+    assert full.full and full.no_cpu_baseline and not full.no_optimizer_leg
+    r = _run(['--steps', '3', '--warmup', '0', '--full'])
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = _run(['--steps', '3', '--warmup', '0', '--no-cpu-baseline'])        # accepted, but said to do nothing without --full
+    assert r.returncode == 0 and 'trim a --full run' in r.stderr, r.stderr[-2000:]
 
 
 def test_every_process_builds_the_same_initial_weights():
