@@ -18,6 +18,7 @@ from .attend import Attend  # noqa: E402
 from .audiolm_pytorch import (AudioLM, CoarseTransformer, CoarseTransformerWrapper, FineTransformer, FineTransformerWrapper,
                               SemanticTransformer, SemanticTransformerWrapper, Transformer, get_embeds)
 from .optimizer import FusedAdam, get_optimizer
+from .resample import resample
 from .soundstream import SoundStream
 from .version import __version__
 

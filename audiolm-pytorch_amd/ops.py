@@ -1051,6 +1051,38 @@ def bct_to_btc(x):
     return out
 
 
+def _rows(x):
+    """fp32 [R, L] with unit element stride -> (tensor, row stride); copies only when the rows are not evenly strided"""
+    if x.stride(-1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x, (x.stride(0) if x.shape[0] > 1 else x.shape[1])
+
+
+def resample_sinc(x, table, o, n, W):
+    """x fp32 [R, L] -> fp32 [R, ceil(n L / o)]: the windowed-sinc polyphase resampler (alm_resample_sinc; table fp32 [n, 2 W + o])."""
+    _chk(x, F32)
+    _chk(table, F32)
+    assert x.dim() == 2 and table.is_contiguous() and table.shape == (n, 2 * W + o)
+    R, L = x.shape
+    x, ld = _rows(x)
+    Lout = (n * L + o - 1) // o
+    out = _new((R, Lout), dtype=F32, device=x.device)
+    _lib.call('alm_resample_sinc', x.data_ptr(), ld, out.data_ptr(), Lout, table.data_ptr(), 2 * W + o, R, L, Lout, o, n, W, _st())
+    return out
+
+
+def resample_sinc_bwd(dy, table, L, o, n, W):
+    """dy fp32 [R, ceil(n L / o)] -> dx fp32 [R, L]: the adjoint of resample_sinc (alm_resample_sinc_bwd)."""
+    _chk(dy, F32)
+    _chk(table, F32)
+    assert dy.dim() == 2 and table.is_contiguous() and table.shape == (n, 2 * W + o)
+    R, Lout = dy.shape
+    dy, ld = _rows(dy)
+    dx = _new((R, L), dtype=F32, device=dy.device)
+    _lib.call('alm_resample_sinc_bwd', dy.data_ptr(), ld, dx.data_ptr(), L, table.data_ptr(), 2 * W + o, R, L, Lout, o, n, W, _st())
+    return dx
+
+
 # ---- SoundStream LocalTransformer (csrc/local_attn.hip), fp32, codec layout [B, C, T]
 
 def layernorm_bct(x, gamma, beta, eps=1e-5):

@@ -29,6 +29,7 @@ import torch
 from torch import nn
 
 from . import core, ops
+from .resample import resample
 
 F32 = torch.float32
 FUSE_RESUNIT = os.environ.get('ALM_FUSE_RESUNIT', '1') != '0'      # A/B switch: 0 = the two alm_conv1d_causal launches per ResidualUnit
@@ -386,10 +387,10 @@ class SoundStream(nn.Module):
         return self.seq_len_multiple_of
 
     def process_input(self, x, input_sample_hz=None, curtail_from_left=False):                   # soundstream.py:779-795
-        if input_sample_hz is not None and input_sample_hz != self.target_sample_hz:
-            raise NotImplementedError('on-the-fly resampling (torchaudio) is outside the hot path: resample before tokenizing')
         lead = x.shape[:-1]
         x = x.reshape(-1, x.shape[-1])                           # pack([x], '* n')
+        if input_sample_hz is not None:                          # torchaudio.functional.resample (resample.py; the same rate returns x itself)
+            x = resample(x, input_sample_hz, self.target_sample_hz)
         x = curtail_to_multiple(x, self.seq_len_multiple_of, from_left=curtail_from_left)
         return x.unsqueeze(1), lead
 

@@ -393,6 +393,18 @@ int alm_rvq_pack(const float* E, float* Et, float* e2, int Q, int C, int d, void
 int alm_rvq_encode(const float* x, long long ldx, const float* E, const float* Et, const float* e2, long long* idx, long long ldi, float* quant,
                    long long ldq, int T, int d, int C, int Q, void* stream);
 int alm_bct_to_btc(const float* in, float* out, int B, int C, int T, void* stream);   /* 'b c n -> b n c', soundstream.py:823 */
+/* input resampling (soundstream.py:779-795: process_input calls torchaudio.functional.resample(x, input_sample_hz, target_sample_hz); torchaudio's
+ * windowed-sinc polyphase resampler, third-party, restated in audiolm-pytorch_amd/resample.py), fp32.  o / n = orig / new rate over their gcd,
+ * table [n][taps] = the sinc kernel (taps = 2 W + o, built on the host), rows of len_in samples x [rows][ld_x] -> len_out = ceil(n len_in / o)
+ * samples y [rows][ld_y]:  y[j n + p] = sum_k table[p][k] x[j o + k - W]  (x = 0 outside [0, len_in)).
+ * _bwd is the adjoint with the same geometry: dy [rows][ld_dy] (len_out) -> dx [rows][ld_dx] (len_in), dx[i] = sum over the (j, p) with
+ * j n + p < len_out and 0 <= i + W - j o < taps of table[p][i + W - j o] dy[j n + p] (a gather: no atomics, bitwise deterministic).
+ * Lengths and strides are 64-bit.  ALM_ERR_BAD_ARG when len_out != ceil(n len_in / o), taps != 2 W + o or a size is negative;
+ * ALM_ERR_UNSUPPORTED when one 8-frame input window exceeds the LDS (o in the tens of thousands). */
+int alm_resample_sinc(const float* x, long long ld_x, float* y, long long ld_y, const float* table, int taps, long long rows, long long len_in,
+                      long long len_out, int o, int n, int W, void* stream);
+int alm_resample_sinc_bwd(const float* dy, long long ld_dy, float* dx, long long ld_dx, const float* table, int taps, long long rows,
+                          long long len_in, long long len_out, int o, int n, int W, void* stream);
 /* SoundStream LocalTransformer (soundstream.py:397-440 = local-attention's LocalMHA + FeedForward; third-party, restated), fp32, in the codec's
  * [B][C][T] layout; the Linear layers are k = 1 alm_conv1d_causal calls.
  *   alm_layernorm_bct : nn.LayerNorm over the channel axis (weight gamma, bias beta)
