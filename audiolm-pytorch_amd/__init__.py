@@ -17,6 +17,7 @@ _lib.load()            # no fallback path exists: fail at import, loudly, if lib
 from .attend import Attend  # noqa: E402
 from .audiolm_pytorch import (AudioLM, CoarseTransformer, CoarseTransformerWrapper, FineTransformer, FineTransformerWrapper,
                               SemanticTransformer, SemanticTransformerWrapper, Transformer, get_embeds)
+from .hubert_kmeans import HubertWithKmeans
 from .optimizer import FusedAdam, get_optimizer
 from .resample import resample
 from .soundstream import SoundStream
@@ -42,4 +43,7 @@ def install_as_reference():
         pkg.SoundStream = soundstream.SoundStream
     except ImportError:
         pass
+    from . import hubert_kmeans
+    sys.modules['audiolm_pytorch.hubert_kmeans'] = hubert_kmeans
+    pkg.HubertWithKmeans = hubert_kmeans.HubertWithKmeans
     return pkg

@@ -116,6 +116,12 @@ SIGNATURES = {
     'alm_bct_to_btc': [_P, _P, _I, _I, _I, _P],
     'alm_resample_sinc': [_P, _L, _P, _L, _P, _I, _L, _L, _L, _I, _I, _I, _P],
     'alm_resample_sinc_bwd': [_P, _L, _P, _L, _P, _I, _L, _L, _L, _I, _I, _I, _P],
+    'alm_hubert_conv0_chunks': [_L],
+    'alm_hubert_conv0_stats': [_P, _L, _P, _P, _P, _I, _I, _L, _L, _I, _I, _F, _P],
+    'alm_hubert_conv0_apply': [_P, _L, _P, _P, _P, _P, _P, _I, _I, _L, _L, _I, _I, _P],
+    'alm_conv1d_valid': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_layernorm_bct_split': [_P, _P, _P, _P, _I, _I, _I, _F, _P],
+    'alm_mha_attn_fwd': [_P, _P, _I, _I, _I, _I, _F, _P],
     'alm_layernorm_bct': [_P, _P, _P, _P, _I, _I, _I, _F, _P],
     'alm_geglu_bct': [_P, _P, _I, _I, _I, _P],
     'alm_local_attn': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],

@@ -1115,3 +1115,78 @@ def local_attn(qkv, q_scale, k_scale, cos_t, sin_t, xpos_t, gates, heads, dim_he
     _lib.call('alm_local_attn', qkv.data_ptr(), q_scale.data_ptr(), k_scale.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(), xpos_t.data_ptr(), _p(gates),
               out.data_ptr(), B, heads, dim_head, T, window, float(scale), _st())
     return out
+
+
+# ---- HuBERT feature model (csrc/hubert.hip) ----
+def hubert_conv0_stats(wave, w, stride, eps=1e-5):
+    """wave fp32 [B, Tin] (unit element stride), w fp32 [C, k] -> stats fp32 [B, C, 2] = (mean, rstd) over time of conv1d(wave, w, stride), the
+    activation never stored (alm_hubert_conv0_stats: shifted sums per chunk, chunks merged in order)."""
+    _chk(wave, F32)
+    _chk(w, F32)
+    assert wave.dim() == 2 and w.dim() == 2 and w.is_contiguous()
+    wave, ld = _rows(wave)
+    B, Tin = wave.shape
+    C, k = w.shape
+    if Tin < k:
+        raise _lib.AlmError(f'the wave has {Tin} samples, fewer than the first conv kernel ({k})')
+    Tout = (Tin - k) // stride + 1
+    part = _new((B, C, _lib.query('alm_hubert_conv0_chunks', Tout), 2), dtype=F32, device=wave.device)
+    stats = _new((B, C, 2), dtype=F32, device=wave.device)
+    _lib.call('alm_hubert_conv0_stats', wave.data_ptr(), ld, w.data_ptr(), part.data_ptr(), stats.data_ptr(), B, C, Tin, Tout, k, stride, float(eps), _st())
+    return stats
+
+
+def hubert_conv0_apply(wave, w, stats, gamma, beta, stride):
+    """-> fp32 [B, C, Tout] = gelu(GroupNorm(C, C)(conv1d(wave, w, stride))) with the statistics of hubert_conv0_stats"""
+    _chk(wave, F32)
+    _chk(stats, F32)
+    wave, ld = _rows(wave)
+    B, Tin = wave.shape
+    C, k = w.shape
+    Tout = (Tin - k) // stride + 1
+    assert stats.shape == (B, C, 2) and stats.is_contiguous() and w.is_contiguous() and gamma.is_contiguous() and beta.is_contiguous()
+    out = _new((B, C, Tout), dtype=F32, device=wave.device)
+    _lib.call('alm_hubert_conv0_apply', wave.data_ptr(), ld, w.data_ptr(), stats.data_ptr(), _chk(gamma, F32).data_ptr(), _chk(beta, F32).data_ptr(),
+              out.data_ptr(), B, C, Tin, Tout, k, stride, _st())
+    return out
+
+
+def conv1d_valid(x, w, bias=None, *, stride=1, pad=0, groups=1, gelu=False, residual=None, drop_last=0):
+    """x fp32 [B, Cin, Tin], w fp32 [Cout, Cin / groups, k] (torch's layout) -> fp32 [B, Cout, Tout], Tout = (Tin + 2 pad - k) // stride + 1 -
+    drop_last: (gelu)(conv + bias) + residual on the exact-fp32 matrix core (alm_conv1d_valid)."""
+    _chk(x, F32)
+    _chk(w, F32)
+    B, Cin, Tin = x.shape
+    Cout, Cig, k = w.shape
+    assert x.is_contiguous() and w.is_contiguous() and Cig * groups == Cin
+    Tout = (Tin + 2 * pad - k) // stride + 1 - drop_last
+    if Tout <= 0:
+        raise _lib.AlmError(f'conv1d_valid: {Tin} input samples give no output (k = {k}, stride = {stride}, pad = {pad})')
+    out = _new((B, Cout, Tout), dtype=F32, device=x.device)
+    if bias is not None:
+        assert _chk(bias, F32).is_contiguous() and bias.shape == (Cout,)
+    if residual is not None:
+        assert _chk(residual, F32).is_contiguous() and residual.shape == out.shape
+    _lib.call('alm_conv1d_valid', x.data_ptr(), w.data_ptr(), _p(bias), _p(residual), out.data_ptr(), B, Cin, Cout, Tin, Tout, k, stride, pad, groups,
+              int(gelu), _st())
+    return out
+
+
+def layernorm_bct_split(x, gamma, beta, eps=1e-5):
+    """nn.LayerNorm over the channel axis of x fp32 [B, C, T], parallel over channels (alm_layernorm_bct_split)"""
+    _chk(x, F32)
+    B, C, T = x.shape
+    assert x.is_contiguous() and gamma.is_contiguous() and beta.is_contiguous() and gamma.shape == beta.shape == (C,)
+    out = _new_like(x)
+    _lib.call('alm_layernorm_bct_split', x.data_ptr(), _chk(gamma, F32).data_ptr(), _chk(beta, F32).data_ptr(), out.data_ptr(), B, C, T, float(eps), _st())
+    return out
+
+
+def mha_attn(qkv, heads, scale=None, dim_head=64):
+    """qkv fp32 [B, 3 H dh, T] (q | k | v channel blocks) -> fp32 [B, H dh, T]: bidirectional multi-head attention (alm_mha_attn_fwd)"""
+    _chk(qkv, F32)
+    B, C3, T = qkv.shape
+    assert qkv.is_contiguous() and C3 == 3 * heads * dim_head
+    out = _new((B, heads * dim_head, T), dtype=F32, device=qkv.device)
+    _lib.call('alm_mha_attn_fwd', qkv.data_ptr(), out.data_ptr(), B, heads, T, dim_head, float(dim_head ** -0.5 if scale is None else scale), _st())
+    return out

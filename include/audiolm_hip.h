@@ -405,6 +405,32 @@ int alm_resample_sinc(const float* x, long long ld_x, float* y, long long ld_y, 
                       long long len_out, int o, int n, int W, void* stream);
 int alm_resample_sinc_bwd(const float* dy, long long ld_dy, float* dx, long long ld_dx, const float* table, int taps, long long rows,
                           long long len_in, long long len_out, int o, int n, int W, void* stream);
+/* ---- HubertWithKmeans (hubert_kmeans.py:37-121): the fairseq HuBERT-base feature model (fairseq models/hubert/hubert.py HubertModel.forward
+ * with features_only, models/wav2vec/wav2vec2.py ConvFeatureExtractionModel / TransformerEncoder / TransformerSentenceEncoderLayer, third-party,
+ * restated in tests/hubert_restated.py) and the k-means assignment (hubert_kmeans.py:114-116).  fp32 on the exact-fp32 matrix core, [B][C][T].
+ * conv0 (wav2vec2.py ConvFeatureExtractionModel, mode 'default': conv(1 -> C, ksize, stride, no bias) + GroupNorm(C, C) + GELU): wave [B][ld_wave]
+ *   (Tin samples per row) -> Tout = (Tin - ksize) / stride + 1.  _stats takes the per-(row, channel) mean / rstd over time without storing the
+ *   activation: part [B][C][alm_hubert_conv0_chunks(Tout)][2] floats of workspace, stats [B][C][2] = (mean, rstd), biased variance, shifted sums
+ *   per chunk merged in chunk order (deterministic, no atomics).  _apply recomputes the conv and writes gelu((c - mean) rstd gamma + beta) to
+ *   out [B][C][Tout].  ksize <= 16, else ALM_ERR_UNSUPPORTED.  Lengths and row offsets are 64-bit. */
+int alm_hubert_conv0_chunks(long long Tout);
+int alm_hubert_conv0_stats(const float* wave, long long ld_wave, const float* w, float* part, float* stats, int B, int C, long long Tin,
+                           long long Tout, int ksize, int stride, float eps, void* stream);
+int alm_hubert_conv0_apply(const float* wave, long long ld_wave, const float* w, const float* stats, const float* gamma, const float* beta,
+                           float* out, int B, int C, long long Tin, long long Tout, int ksize, int stride, void* stream);
+/* conv1d with symmetric zero padding `pad` and `groups` (wav2vec2.py conv layers 1..6: pad 0, GELU; TransformerEncoder.pos_conv + SamePad + GELU
+ * + the residual add of extract_features: groups 16, k 128, pad 64, Tout = Tin; the nn.Linear layers: k 1): x [B][Cin][Tin], w [Cout][Cin / groups]
+ * [ksize] (torch's layout, unpacked), out [B][Cout][Tout] = (gelu ? erf-GELU : id)(conv + bias) + residual; bias / residual may be NULL.
+ * Tout <= (Tin + 2 pad - ksize) / stride + 1 (a smaller Tout drops trailing outputs), else ALM_ERR_BAD_ARG.  Batch and channel-row offsets are
+ * 64-bit; in-row indices are 32-bit, ALM_ERR_UNSUPPORTED when (Tout + 64) stride + ksize or (Cin / groups) ksize reaches 2^31. */
+int alm_conv1d_valid(const float* x, const float* w, const float* bias, const float* residual, float* out, int B, int Cin, int Cout, int Tin,
+                     int Tout, int ksize, int stride, int pad, int groups, int gelu, void* stream);
+/* nn.LayerNorm over the channel axis of [B][C][T] (wav2vec2.py: layer_norm, encoder.layer_norm, self_attn_layer_norm, final_layer_norm), the
+ * arguments of alm_layernorm_bct; 32 channel slices per time step and a two-pass variance, for sequences too short to fill the chip one thread per t. */
+int alm_layernorm_bct_split(const float* x, const float* gamma, const float* beta, float* out, int B, int C, int T, float eps, void* stream);
+/* fairseq MultiheadAttention (self-attention, no mask, eval): qkv [B][3 H dim_head][T] (q | k | v channel blocks) -> out [B][H dim_head][T] =
+ * softmax((scale q) . k) v per head, flash style (online softmax, no score matrix in memory).  dim_head == 64, else ALM_ERR_UNSUPPORTED. */
+int alm_mha_attn_fwd(const float* qkv, float* out, int B, int H, int T, int dim_head, float scale, void* stream);
 /* SoundStream LocalTransformer (soundstream.py:397-440 = local-attention's LocalMHA + FeedForward; third-party, restated), fp32, in the codec's
  * [B][C][T] layout; the Linear layers are k = 1 alm_conv1d_causal calls.
  *   alm_layernorm_bct : nn.LayerNorm over the channel axis (weight gamma, bias beta)
