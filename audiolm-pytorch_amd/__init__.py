@@ -2,7 +2,7 @@
 
 The directory is called `audiolm-pytorch_amd/` (repo contract); import it as `audiolm_pytorch_amd` through the loader module
 `audiolm_pytorch_amd.py` at the repo root.  `install_as_reference()` additionally registers these modules under the reference's
-import paths (`audiolm_pytorch.audiolm_pytorch`, `.attend`, `.soundstream`) so that an unmodified reference trainer.py picks
+import paths (`audiolm_pytorch.audiolm_pytorch`, `.attend`, `.soundstream`, `.t5`) so that an unmodified reference trainer.py picks
 them up.
 """
 from __future__ import annotations
@@ -21,6 +21,7 @@ from .hubert_kmeans import HubertWithKmeans
 from .optimizer import FusedAdam, get_optimizer
 from .resample import resample
 from .soundstream import SoundStream
+from .t5 import T5Encoder, load_t5, register_t5, t5_encode_text
 from .version import __version__
 
 
@@ -46,4 +47,7 @@ def install_as_reference():
     from . import hubert_kmeans
     sys.modules['audiolm_pytorch.hubert_kmeans'] = hubert_kmeans
     pkg.HubertWithKmeans = hubert_kmeans.HubertWithKmeans
+    from . import t5
+    sys.modules['audiolm_pytorch.t5'] = t5                        # audiolm_pytorch.py:31 `from audiolm_pytorch.t5 import t5_encode_text, ...`
+    pkg.t5 = t5
     return pkg

@@ -122,6 +122,10 @@ SIGNATURES = {
     'alm_conv1d_valid': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'alm_layernorm_bct_split': [_P, _P, _P, _P, _I, _I, _I, _F, _P],
     'alm_mha_attn_fwd': [_P, _P, _I, _I, _I, _I, _F, _P],
+    'alm_t5_embed': [_P, _P, _P, _I, _I, _L, _P, _P],
+    'alm_t5_rmsnorm': [_P, _P, _P, _P, _I, _I, _F, _I, _P],
+    'alm_t5_gate': [_P, _P, _L, _L, _I, _P],
+    'alm_t5_attn_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     'alm_layernorm_bct': [_P, _P, _P, _P, _I, _I, _I, _F, _P],
     'alm_geglu_bct': [_P, _P, _I, _I, _I, _P],
     'alm_local_attn': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],

@@ -16,7 +16,8 @@ parameter containers + integer bookkeeping; every floating-point op of the path 
 
 Conditioning (`has_condition=True`, reference :325-375, :450-455, :640-668, :818-855, :1097-1134): cross-attention layers with a null key / value,
 `cond_as_self_attn_prefix`, per-sample condition dropping and classifier-free guidance all run natively from pre-computed `text_embeds`
-(xattn.py / csrc/xattn.hip); the T5 text encoder is out of scope (`text=` raises).
+(xattn.py / csrc/xattn.hip), or from `text=` through the native T5 encoder (t5.py / csrc/t5.hip) once a local T5 is registered under the
+transformer's `t5_name` (t5.register_t5 / load_t5); with none registered `text=` raises NotImplementedError (hub names are never resolved).
 The reference's stacked kv_cache= / embed_cache= TENSOR protocol is accepted on forward() / forward_with_cond_scale()
 (Transformer.forward_kv_protocol: the one-new-token step runs the same single-position kernels); generate() drives the native cache directly.
 An arbitrary dense `attn_bias` tensor takes the reference's O(n^2) math path (relpos.DenseBias, xattn.py) instead of the flash kernels.
@@ -39,19 +40,11 @@ from torch import nn
 
 from . import core, heads, ops, relpos
 from .attend import Attend
+from .t5 import DEFAULT_T5_NAME, _T5_DIMS, get_encoded_dim, t5_encode_text  # noqa: F401  (reference audiolm_pytorch.py:31)
 from .version import __version__
 
-DEFAULT_T5_NAME = 'google/t5-v1_1-base'
 FUSED_PREPARE = os.environ.get('ALM_FUSED_PREPARE', '1') != '0'      # Coarse wrapper's training step / FineTransformer's assembly: id bookkeeping as one kernel (A/B switch, tests)
 DECODE_GRAPH = os.environ.get('ALM_DECODE_GRAPH', '1') != '0'        # capture the single-position sampling step into a hipGraph
-_T5_DIMS = {'google/t5-v1_1-small': 512, 'google/t5-v1_1-base': 768, 'google/t5-v1_1-large': 1024,
-            'google/t5-v1_1-xl': 2048, 'google/t5-v1_1-xxl': 4096, 't5-small': 512, 't5-base': 768, 't5-large': 1024}
-
-
-def get_encoded_dim(name):
-    """reference t5.py:get_encoded_dim needs the HF hub; text conditioning is out of scope, only the width is needed so that
-    `proj_text_embed` keeps the reference's shape in the state_dict (audiolm_pytorch.py:604-605)."""
-    return _T5_DIMS.get(name, 768)
 
 
 # ---------------------------------------------------------------------------------------------- helpers (audiolm_pytorch.py:40-186)
@@ -889,8 +882,8 @@ class _TransformerBase(nn.Module):
 
     def _condition(self, b, device, text, text_embeds, cond_drop_prob, mask_from_embeds):
         """Conditioning of one forward (audiolm_pytorch.py:685-704 / :873-892 / :1150-1169): -> (context [b, m, dim] | None, context_mask bool
-        [b, m] | None).  `text_embeds` are the pre-computed T5 / MuLaN embeddings (the text encoder itself is out of scope); positions whose
-        embedding is all zero are padding.  Quirk kept: Semantic- and FineTransformer derive the mask only when they ran the text encoder
+        [b, m] | None).  `text_embeds` are pre-computed T5 / MuLaN embeddings, `text` goes through the registered T5 encoder (t5.py); positions
+        whose embedding is all zero are padding.  Quirk kept: Semantic- and FineTransformer derive the mask only when they ran the text encoder
         themselves (:692-695, :1156-1160), so with pre-computed embeddings they have no mask and `cond_drop_prob` has nothing to drop
         (mask_from_embeds=False); CoarseTransformer takes the mask from the embeddings (:882-883)."""
         has_text = exists(text) or exists(text_embeds)
@@ -901,6 +894,8 @@ class _TransformerBase(nn.Module):
         if not exists(text_embeds):
             with torch.inference_mode():
                 text_embeds = self.embed_text(text, output_device=device)
+            if text_embeds.is_inference() and not torch.is_inference_mode_enabled():
+                text_embeds = text_embeds.clone()          # an inference tensor cannot be saved for the backward of proj_text_embed
             if not mask_from_embeds:
                 text_mask = torch.any(text_embeds != 0, dim=-1)
         if mask_from_embeds:
@@ -983,11 +978,9 @@ class _TransformerBase(nn.Module):
             cond_dim = default(cond_dim, dim)
         self.has_condition = has_condition
         self.cond_drop_prob = cond_drop_prob
+        self.embed_text = partial(t5_encode_text, name=t5_name)      # reference :596 / :761 / :1025
         text_dim = default(cond_dim, get_encoded_dim(t5_name))
         self.proj_text_embed = nn.Linear(text_dim, dim, bias=False) if text_dim != dim else nn.Identity()
-
-    def embed_text(self, *a, **k):
-        raise NotImplementedError('the T5 text encoder is out of scope (SURVEY.md §2): pass pre-computed `text_embeds` (b, m, cond_dim) instead of `text`')
 
     def _heads_cache(self):
         return self.transformer._cache
@@ -1790,7 +1783,7 @@ class FineTransformerWrapper(_WrapperBase):                   # audiolm_pytorch.
 
 class AudioLM(nn.Module):                                     # audiolm_pytorch.py:2141-2254
     """Hierarchical sampling: semantic -> coarse -> fine -> waveform, every stage on the native path (kv-cache sampling, SoundStream decoder).
-    Conditioned transformers take pre-computed `text_embeds` (or an audio conditioner callable); the T5 text encoder itself is out of scope."""
+    Conditioned transformers take `text` (encoded once per call by the registered T5, t5.py), pre-computed `text_embeds`, or an audio conditioner."""
 
     def __init__(self, *, wav2vec, codec, semantic_transformer: SemanticTransformer, coarse_transformer: CoarseTransformer,
                  fine_transformer: FineTransformer, audio_conditioner=None, unique_consecutive=True):

@@ -810,7 +810,8 @@ def device_error_flag(device):
     IndexError; the kernels never dereference such an id).  Poll it with check_device_errors() at a point where a sync is acceptable."""
     key = (device.type, device.index)
     if key not in _err_flags:
-        _err_flags[key] = torch.zeros(1, dtype=torch.int32, device=device)
+        with torch.inference_mode(False):       # the word outlives the call: created under inference_mode (a text= encode, generate()) it could not be zeroed later
+            _err_flags[key] = torch.zeros(1, dtype=torch.int32, device=device)
     return _err_flags[key]
 
 
@@ -843,7 +844,8 @@ def poll_device_errors(device):
         return
     st = _err_poll.get(key)
     if st is None:
-        st = _err_poll[key] = [torch.zeros(1, dtype=torch.int32).pin_memory(), None]
+        with torch.inference_mode(False):       # as device_error_flag: the pinned copy is written by later calls outside inference_mode
+            st = _err_poll[key] = [torch.zeros(1, dtype=torch.int32).pin_memory(), None]
     host, ev = st
     if ev is not None:
         if not ev.query():
@@ -1189,4 +1191,58 @@ def mha_attn(qkv, heads, scale=None, dim_head=64):
     assert qkv.is_contiguous() and C3 == 3 * heads * dim_head
     out = _new((B, heads * dim_head, T), dtype=F32, device=qkv.device)
     _lib.call('alm_mha_attn_fwd', qkv.data_ptr(), out.data_ptr(), B, heads, T, dim_head, float(dim_head ** -0.5 if scale is None else scale), _st())
+    return out
+
+
+# ---- T5 text encoder (csrc/t5.hip): activations fp32 [C, N], N = B * T columns ----
+def t5_embed(ids, table):
+    """ids int64 [B, T], table fp32 [vocab, D] -> fp32 [D, B * T] (alm_t5_embed).  An id outside the table is embedded as zeros and raises the
+    device error word (see device_error_flag), polled like the other embedding lookups."""
+    _chk(table, F32)
+    if not ids.is_cuda or ids.dtype != torch.int64:
+        raise _lib.AlmError('t5_embed: ids must be an int64 tensor on the GPU')
+    assert ids.is_contiguous() and table.is_contiguous() and table.dim() == 2
+    N, (vocab, D) = ids.numel(), table.shape
+    out = _new((D, N), dtype=F32, device=ids.device)
+    poll_device_errors(ids.device)
+    _lib.call('alm_t5_embed', ids.data_ptr(), table.data_ptr(), out.data_ptr(), N, D, vocab, device_error_flag(ids.device).data_ptr(), _st())
+    return out
+
+
+def t5_rmsnorm(x, weight, eps=1e-6, mask=None, transpose_out=False):
+    """T5LayerNorm over the channel axis of x fp32 [C, N]: weight * x * rsqrt(mean(x^2) + eps) -> [C, N], or [N, C] with transpose_out.
+    mask uint8 [N]: exact zeros where it is 0 (alm_t5_rmsnorm)."""
+    _chk(x, F32)
+    C, N = x.shape
+    assert x.is_contiguous() and _chk(weight, F32).is_contiguous() and weight.shape == (C,)
+    if mask is not None:
+        assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() == N
+    out = _new((N, C) if transpose_out else (C, N), dtype=F32, device=x.device)
+    _lib.call('alm_t5_rmsnorm', x.data_ptr(), weight.data_ptr(), _p(mask), out.data_ptr(), C, N, float(eps), int(transpose_out), _st())
+    return out
+
+
+def t5_gate(x, gated=True):
+    """gated: x fp32 [2 F, N] -> [F, N] = gelu_new(x[:F]) * x[F:]; else x [F, N] -> relu(x) (alm_t5_gate)"""
+    _chk(x, F32)
+    R, N = x.shape
+    assert x.is_contiguous() and (not gated or R % 2 == 0)
+    Fdim = R // 2 if gated else R
+    out = _new((Fdim, N), dtype=F32, device=x.device)
+    _lib.call('alm_t5_gate', x.data_ptr(), out.data_ptr(), Fdim, N, int(gated), _st())
+    return out
+
+
+def t5_attn(qkv, bias, mask, B, heads, dim_head=64):
+    """qkv fp32 [3 H dh, B * T], bias fp32 [H, 2 T - 1] (entry j - i + T - 1 for key j, query i), mask uint8 [B, T] | None -> fp32 [H dh, B * T]:
+    T5's bidirectional self-attention, no 1 / sqrt(d) scale (alm_t5_attn_fwd)"""
+    _chk(qkv, F32)
+    _chk(bias, F32)
+    C3, N = qkv.shape
+    T = N // B
+    assert qkv.is_contiguous() and bias.is_contiguous() and C3 == 3 * heads * dim_head and T * B == N and tuple(bias.shape) == (heads, 2 * T - 1)
+    if mask is not None:
+        assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() == N
+    out = _new((heads * dim_head, N), dtype=F32, device=qkv.device)
+    _lib.call('alm_t5_attn_fwd', qkv.data_ptr(), bias.data_ptr(), _p(mask), out.data_ptr(), B, heads, T, dim_head, _st())
     return out

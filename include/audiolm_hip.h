@@ -431,6 +431,22 @@ int alm_layernorm_bct_split(const float* x, const float* gamma, const float* bet
 /* fairseq MultiheadAttention (self-attention, no mask, eval): qkv [B][3 H dim_head][T] (q | k | v channel blocks) -> out [B][H dim_head][T] =
  * softmax((scale q) . k) v per head, flash style (online softmax, no score matrix in memory).  dim_head == 64, else ALM_ERR_UNSUPPORTED. */
 int alm_mha_attn_fwd(const float* qkv, float* out, int B, int H, int T, int dim_head, float scale, void* stream);
+
+/* ---- T5 text encoder (csrc/t5.hip): transformers T5Stack (encoder) as the reference's t5.py:68-110 calls it, restated in tests/t5_restated.py.
+ * fp32, inference only.  Activations are [C][N], N = B T columns (sample b = columns b T .. b T + T - 1); the bias-less Linear layers are
+ * alm_conv1d_valid with B = 1, ksize = 1, Tin = N.
+ * _embed: ids int64 [N] -> out [D][N] = table[ids[n]][c], table [vocab][D].  An id outside [0, vocab) is not dereferenced: zero column and
+ *   *err_flag = 1 (err_flag may be NULL).
+ * _rmsnorm: T5LayerNorm, out = w x rsqrt(mean_c(x^2) + eps) (no mean subtraction, no bias), fixed summation order.  mask uint8 [N] or NULL:
+ *   columns with mask 0 are written as exact 0.0.  transpose_out: out is [N][C] row-major instead of [C][N].  out must not alias x.
+ * _gate: gated: x [2 F][N] -> out [F][N] = gelu_new(x[f]) x[F + f] (tanh form of GELU); else x [F][N] -> relu(x).
+ * _attn_fwd: qkv [3 H 64][N] (q | k | v channel blocks, q unscaled) -> out [H 64][N] = softmax_j(q_i . k_j + bias[h][j - i + T - 1]) v_j over the
+ *   keys j of the same sample with mask[b][j] != 0; bias [H][2 T - 1], mask uint8 [B][T] or NULL.  A masked key has probability exactly 0; a
+ *   sample with every key masked gives zeros.  dim_head == 64 and T <= 2048, else ALM_ERR_UNSUPPORTED. */
+int alm_t5_embed(const long long* ids, const float* table, float* out, int N, int D, long long vocab, int* err_flag, void* stream);
+int alm_t5_rmsnorm(const float* x, const float* w, const unsigned char* mask, float* out, int C, int N, float eps, int transpose_out, void* stream);
+int alm_t5_gate(const float* x, float* out, long long F, long long N, int gated, void* stream);
+int alm_t5_attn_fwd(const float* qkv, const float* bias, const unsigned char* mask, float* out, int B, int H, int T, int dim_head, void* stream);
 /* SoundStream LocalTransformer (soundstream.py:397-440 = local-attention's LocalMHA + FeedForward; third-party, restated), fp32, in the codec's
  * [B][C][T] layout; the Linear layers are k = 1 alm_conv1d_causal calls.
  *   alm_layernorm_bct : nn.LayerNorm over the channel axis (weight gamma, bias beta)

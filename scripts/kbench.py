@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5]"""
 import os
 import sys
 import time
@@ -474,6 +474,45 @@ def bench_misc():
     dy = rnd(M, D)
     t = timeit(lambda: ops.layernorm_bwd(dy, x, mean, rstd, g))
     print(f'layernorm_bwd: {t:.3f} ms  {(M * D * 8) / t / 1e6:.0f} GB/s')
+
+
+def bench_t5():
+    """native T5Encoder.forward at t5-v1_1-base size against the plain-torch restatement (tests/t5_restated.py) in fp32 eager torch on the same GPU in
+    the same process: what a user of text= has without this package's encoder.  One event pair per forward, median of 30 after 5 warm-up runs."""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import t5_restated as TR
+    sd = TR.random_state_dict(11)
+    enc = A.T5Encoder.from_state_dict(sd, num_heads=12).to(dev)
+    sdg = {k: v.to(dev) for k, v in sd.items()}
+    mmac = lambda T: 12 * (4 * 768 * 768 + 3 * 768 * 2048 + 2 * T * 768) / 1e6                   # noqa: E731  per token
+
+    def median_ms(fn, iters=30, warm=5):
+        for _ in range(warm):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        return ts[len(ts) // 2], ts[0], ts[-1]
+    for B, T, lengths in ((8, 256, [256, 1, 17, 100, 255, 33, 64, 200]), (8, 24, [24, 10, 17, 12, 21, 5, 14, 19])):
+        ids = torch.randint(0, 512, (B, T), device=dev)
+        mask = (torch.arange(T, device=dev)[None, :] < torch.tensor(lengths, device=dev)[:, None]).long()
+        pb = TR.position_bias(sd[TR.BIAS_KEY], T).to(dev)          # once, outside the timed call: transformers builds its bias on the device
+        with torch.no_grad():
+            nat = median_ms(lambda: enc(ids, mask))
+            ref = median_ms(lambda: TR.encode(sdg, ids, mask, heads=12, gated=True, bias=pb))
+            err = relerr(enc(ids, mask), TR.encode(sdg, ids, mask, heads=12, gated=True))
+        flop = 2 * mmac(T) * 1e6 * B * T
+        floor = flop / 157.3e12 * 1e3
+        print(f't5 v1.1-base {B} x {T}: native {nat[0]:.3f} ms (min {nat[1]:.3f}, max {nat[2]:.3f}; {flop / nat[0] / 1e9:.1f} TFLOP/s, '
+              f'{nat[0] / floor:.2f} x the {floor:.3f} ms fp32 matrix-peak floor)   eager torch fp32 {ref[0]:.3f} ms (min {ref[1]:.3f}, max {ref[2]:.3f})   '
+              f'native / eager {nat[0] / ref[0]:.2f}   max rel diff {err:.1e}')
 
 
 if __name__ == '__main__':
