@@ -2,7 +2,7 @@
 
 The directory is called `audiolm-pytorch_amd/` (repo contract); import it as `audiolm_pytorch_amd` through the loader module
 `audiolm_pytorch_amd.py` at the repo root.  `install_as_reference()` additionally registers these modules under the reference's
-import paths (`audiolm_pytorch.audiolm_pytorch`, `.attend`, `.soundstream`, `.t5`) so that an unmodified reference trainer.py picks
+import paths (`audiolm_pytorch.audiolm_pytorch`, `.attend`, `.soundstream`, `.encodec`, `.t5`) so that an unmodified reference trainer.py picks
 them up.
 """
 from __future__ import annotations
@@ -17,6 +17,7 @@ _lib.load()            # no fallback path exists: fail at import, loudly, if lib
 from .attend import Attend  # noqa: E402
 from .audiolm_pytorch import (AudioLM, CoarseTransformer, CoarseTransformerWrapper, FineTransformer, FineTransformerWrapper,
                               SemanticTransformer, SemanticTransformerWrapper, Transformer, get_embeds)
+from .encodec import EncodecWrapper
 from .hubert_kmeans import HubertWithKmeans
 from .optimizer import FusedAdam, get_optimizer
 from .resample import resample
@@ -47,6 +48,9 @@ def install_as_reference():
     from . import hubert_kmeans
     sys.modules['audiolm_pytorch.hubert_kmeans'] = hubert_kmeans
     pkg.HubertWithKmeans = hubert_kmeans.HubertWithKmeans
+    from . import encodec
+    sys.modules['audiolm_pytorch.encodec'] = encodec              # trainer.py:37 `from audiolm_pytorch.encodec import EncodecWrapper`
+    pkg.EncodecWrapper = encodec.EncodecWrapper
     from . import t5
     sys.modules['audiolm_pytorch.t5'] = t5                        # audiolm_pytorch.py:31 `from audiolm_pytorch.t5 import t5_encode_text, ...`
     pkg.t5 = t5

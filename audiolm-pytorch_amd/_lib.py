@@ -129,6 +129,9 @@ SIGNATURES = {
     'alm_layernorm_bct': [_P, _P, _P, _P, _I, _I, _I, _F, _P],
     'alm_geglu_bct': [_P, _P, _I, _I, _I, _P],
     'alm_local_attn': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    'alm_conv1d_causal_pre': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_lstm_launches': [_I, _I],
+    'alm_lstm_seq': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     'alm_memset_zero': [_P, _L, _P],
     'alm_list_op_id': [ctypes.c_char_p],
     'alm_list_op_nargs': [_I],

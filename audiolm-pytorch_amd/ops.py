@@ -1246,3 +1246,40 @@ def t5_attn(qkv, bias, mask, B, heads, dim_head=64):
     out = _new((heads * dim_head, N), dtype=F32, device=qkv.device)
     _lib.call('alm_t5_attn_fwd', qkv.data_ptr(), bias.data_ptr(), _p(mask), out.data_ptr(), B, heads, T, dim_head, _st())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ EnCodec (csrc/encodec.hip)
+
+def conv1d_causal_pre(x, wp, bias, Cout, ksize, *, stride=1, dilation=1, pre_elu=False, elu=False, residual=None, zero_pad=False):
+    """conv1d_causal with a pre-activation: act(bias + conv(ELU(x) if pre_elu else x)) (+ residual); x fp32 [B, Cin, T] -> [B, Cout, T // stride]."""
+    _chk(x, F32)
+    B, Cin, T = x.shape
+    assert x.is_contiguous()
+    out = _new((B, Cout, (T - stride) // stride + 1), dtype=F32, device=x.device)
+    if residual is not None:
+        assert residual.shape == out.shape and residual.is_contiguous()
+    _lib.call('alm_conv1d_causal_pre', x.data_ptr(), wp.data_ptr(), bias.data_ptr(), _p(residual), out.data_ptr(), B, Cin, Cout, T, ksize, stride,
+              dilation, int(pre_elu), int(elu), int(zero_pad), _st())
+    return out
+
+
+def lstm_launches(T, L):
+    return _lib.query('alm_lstm_launches', T, L)
+
+
+def lstm_seq(xproj, w_ih, w_hh, bias, *, skip=None, out_bct=False):
+    """nn.LSTM(H, H, L) over time: xproj fp32 [T, B, 4H] (layer 0's input projection, no bias), w_ih / w_hh [L, 4H, H], bias [L, 4H] (b_ih + b_hh)
+    -> the last layer's outputs [T, B, H], or with out_bct [B, H, T] (+ skip [T, B, H]).  One launch per step, all from one C call (alm_lstm_seq)."""
+    _chk(xproj, F32)
+    T, B, H4 = xproj.shape
+    L, H = w_hh.shape[0], w_hh.shape[2]
+    assert H4 == 4 * H and w_hh.shape == w_ih.shape == (L, 4 * H, H) and bias.shape == (L, 4 * H)
+    assert all(_chk(t, F32).is_contiguous() for t in (xproj, w_ih, w_hh, bias))
+    hseq = _new((L, T, B, H), dtype=F32, device=xproj.device)
+    c = _new((L, B, H), dtype=F32, device=xproj.device)
+    out = _new((B, H, T), dtype=F32, device=xproj.device) if out_bct else None
+    if skip is not None:
+        assert out_bct and _chk(skip, F32).is_contiguous() and skip.shape == (T, B, H)
+    _lib.call('alm_lstm_seq', xproj.data_ptr(), w_ih.data_ptr(), w_hh.data_ptr(), bias.data_ptr(), hseq.data_ptr(), c.data_ptr(), _p(skip), _p(out),
+              T, B, H, L, _st())
+    return out if out_bct else hseq[L - 1]

@@ -460,6 +460,19 @@ int alm_geglu_bct(const float* x, float* out, int B, int I, int T, void* stream)
 int alm_local_attn(const float* qkv, const float* q_scale, const float* k_scale, const float* cos_t, const float* sin_t, const float* xpos_t,
                    const float* gates, float* out, int B, int H, int dim_head, int T, int window, float scale, void* stream);
 
+/* ---- EnCodec 24 kHz (csrc/encodec.hip): the causal SEANet encoder / decoder and LSTM that the reference's encodec.py:25-177 runs through Meta's model,
+ * restated in tests/encodec_restated.py.  fp32.  The residual VQ is alm_rvq_pack / alm_rvq_encode / alm_rvq_decode above.
+ * alm_conv1d_causal_pre = alm_conv1d_causal with `pre_elu`: out = act(bias + conv(pre_elu ? ELU(x) : x)) (+ residual) -- SEANet applies ELU before each conv.
+ * alm_lstm_seq: nn.LSTM(H, H, L), gate order i f g o, zero initial state, one launch per time step issued from this one call (alm_lstm_launches(T, L) =
+ * T + L - 1 launches: launch t advances layer l to time t - l; no workgroup waits for another one).  xproj [T][B][4H] = W_ih_l0 x_t without bias,
+ * w_ih / w_hh [L][4H][H] (w_ih's layer-0 slice is not read), bias [L][4H] = b_ih + b_hh, hseq [L][T][B][H] (every layer's outputs), c [L][B][H] scratch;
+ * optional skip [T][B][H] and out [B][H][T] = the last layer's h (+ skip).  H <= 1024, else ALM_ERR_UNSUPPORTED. */
+int alm_conv1d_causal_pre(const float* x, const float* wp, const float* bias, const float* residual, float* out, int B, int Cin, int Cout, int Tin,
+                          int ksize, int stride, int dilation, int pre_elu, int elu, int zero_pad, void* stream);
+int alm_lstm_launches(int T, int L);
+int alm_lstm_seq(const float* xproj, const float* w_ih, const float* w_hh, const float* bias, float* hseq, float* c, const float* skip, float* out,
+                 int T, int B, int H, int L, void* stream);
+
 /* ---- launch lists (round 6): a recorded sequence of the launches above re-issued by ONE host call ---------------------------------------------
  * The depth loop of audiolm_pytorch.py:528-547 (Transformer.forward) and its backward are ~190 launches per training step whose ORDER and scalar arguments
  * depend only on the model configuration and the batch shape; only buffer addresses change between steps.  The host records the sequence once per shape
