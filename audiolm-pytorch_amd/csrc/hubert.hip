@@ -7,20 +7,12 @@
 //                    the chunk's first 32 outputs (a DC-heavy wave does not cancel); stage 2 = one thread per (row, channel) merging the chunks in index order
 //                    (Chan's update, fp64).  No atomics: bitwise deterministic.
 //   conv0 apply    : recomputes the conv (same fma chain), normalises, GELU, stores [B][C][T0] once.
-//   conv1d_valid   : implicit GEMM of an unpadded / zero-padded, strided, grouped conv1d: 64 (Cout) x 64 (T) tile per workgroup of 4 waves, each
-//                    wave a 32 x 32 block; the reduction index r = ci * ksize + k runs in chunks of 32 through LDS (weights [64][32], im2col'd
-//                    input [32][64]); the next chunk's global loads are in flight while the matrix core works on the current one.
-//                    Epilogue: + bias, erf-GELU, + residual.  k = 1 is the Linear layers; groups = 16, k = 128, pad = 64 the positional conv.
 //   layernorm      : nn.LayerNorm over channels, 32 channel slices per time step (alm_layernorm_bct's one thread per t starves at n <= 1499).
-//   mha_attn       : bidirectional multi-head attention, head width 64, flash style: a wave owns 32 queries (Q^T in registers, pre-scaled as
-//                    fairseq scales q), walks the keys 32 at a time from LDS, S^T = K Q^T puts one query per lane so that the online-softmax
-//                    row statistics are in-lane plus ONE exchange with lane ^ 32; P^T feeds O^T = V^T P^T straight from the accumulator
-//                    registers (the key order of that sum is the accumulator's row order on both operands).
+//   conv1d_valid (the convs after layer 0, every Linear, the positional conv) and mha_attn (the attention) are the shared fp32 kernels of
+//   dense_f32.hip.
 #include "common.hpp"
 
 namespace {
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 
 constexpr int C0_CHUNK = 1024;        // conv0 outputs per statistics chunk
 constexpr int C0_MAXK = 16;
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restric
         for (int k = 0; k < C0_MAXK; ++k)
             if (k < ksize) v = fmaf(ws[cl][k], xv[k], v);
         const float4 a = aff[cl];
-        dst[(size_t)cl * Tout] = gelu_erf((v - a.x) * a.y * a.z + a.w);
+        dst[(size_t)cl * Tout] = gelu_f((v - a.x) * a.y * a.z + a.w);
     }
 }
 
@@ -170,176 +162,6 @@ __global__ __launch_bounds__(1024) void ln_bct_split_kernel(const float* __restr
     for (int c = sl; c < C; c += NS) op[(size_t)c * T] = (xp[(size_t)c * T] - mean) * rstd * gamma[c] + beta[c];
 }
 
-// ---- general conv1d as an implicit GEMM on the fp32 matrix core ----
-struct ConvArgs {
-    const float* x; const float* w; const float* bias; const float* res; float* out;
-    int Cin, Cout, Tin, Tout, ksize, stride, pad, groups, gelu;
-};
-constexpr int CV_RK = 32;
-
-template <int KS>
-__global__ __launch_bounds__(256) void conv_valid_kernel(ConvArgs a) {
-    __shared__ float As[64][CV_RK + 1];
-    __shared__ float Bs[CV_RK][64];
-    const int ks = KS ? KS : a.ksize;
-    const int Cig = a.Cin / a.groups, Cog = a.Cout / a.groups;
-    const int R = Cig * ks;
-    const int tiles_co = (Cog + 63) / 64;
-    const int g = blockIdx.y / tiles_co, co0 = (blockIdx.y % tiles_co) * 64;
-    const int t0 = blockIdx.x * 64, b = blockIdx.z;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lr = lane & 31, lh = lane >> 5, wm = wave >> 1, wn = wave & 1;
-    const float* xb = a.x + ((size_t)b * a.Cin + (size_t)g * Cig) * a.Tin;
-    const float* wg = a.w + (size_t)g * Cog * R;
-
-    const int ar = tid & 31, aco = tid >> 5;          // A: r = ar, co = aco + 8 i
-    const int bt = tid & 63, br = tid >> 6;           // B: t = bt, r = br + 4 i
-    const bool tok = t0 + bt < a.Tout;
-    const int tbase = (t0 + bt) * a.stride - a.pad;
-    float areg[8], breg[8];
-    auto load = [&](int r0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int co = co0 + aco + 8 * i, r = r0 + ar;
-            areg[i] = (co < Cog && r < R) ? wg[(size_t)co * R + r] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int rr = r0 + br + 4 * i;
-            const int ci = rr / ks, k = rr - ci * ks;
-            const int ti = tbase + k;
-            breg[i] = (tok && rr < R && ti >= 0 && ti < a.Tin) ? xb[(size_t)ci * a.Tin + ti] : 0.f;
-        }
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) As[aco + 8 * i][ar] = areg[i];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) Bs[br + 4 * i][bt] = breg[i];
-    };
-    f32x16 acc;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-    load(0);
-    stage();
-    __syncthreads();
-    for (int r0 = 0; r0 < R; r0 += CV_RK) {
-        const bool more = r0 + CV_RK < R;
-        if (more) load(r0 + CV_RK);
-#pragma unroll
-        for (int kk = 0; kk < CV_RK / 2; ++kk)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[wm * 32 + lr][2 * kk + lh], Bs[2 * kk + lh][wn * 32 + lr], acc, 0, 0, 0);
-        __syncthreads();
-        if (more) {
-            stage();
-            __syncthreads();
-        }
-    }
-    const int t = t0 + wn * 32 + lr;
-    if (t >= a.Tout) return;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int co = co0 + wm * 32 + (v & 3) + 8 * (v >> 2) + 4 * lh;
-        if (co < Cog) {
-            const int cg = g * Cog + co;
-            float y = acc[v];
-            if (a.bias) y += a.bias[cg];
-            if (a.gelu) y = gelu_erf(y);
-            const size_t o = ((size_t)b * a.Cout + cg) * a.Tout + t;
-            if (a.res) y += a.res[o];
-            a.out[o] = y;
-        }
-    }
-}
-
-// ---- bidirectional multi-head attention, head width 64: qkv [B][3 H 64][T] -> out [B][H 64][T] ----
-__global__ __launch_bounds__(256) void mha_attn_kernel(const float* __restrict__ qkv, float* __restrict__ out, int H, int T, float scale) {
-    __shared__ float Ks[64][32];
-    __shared__ float Vs[64][33];
-    const int b = blockIdx.z, h = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lr = lane & 31, lh = lane >> 5;
-    const int D = H * 64;
-    const int q = blockIdx.x * 128 + wave * 32 + lr;
-    const float* base = qkv + (size_t)b * 3 * D * T;
-    const float* Q = base + (size_t)(h * 64) * T;
-    const float* K = base + (size_t)(D + h * 64) * T;
-    const float* V = base + (size_t)(2 * D + h * 64) * T;
-
-    float qreg[32];
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) qreg[kk] = q < T ? Q[(size_t)(2 * kk + lh) * T + q] * scale : 0.f;
-    f32x16 o0, o1;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) { o0[v] = 0.f; o1[v] = 0.f; }
-    float m = -INFINITY, l = 0.f;
-
-    const int lkey = tid & 31, ld0 = tid >> 5;        // tile loads: key = lkey, d = ld0 + 8 i
-    float kreg[8], vreg[8];                           // the next tile, in flight while the matrix core works on the current one
-    auto fetch = [&](int k0) {
-        const bool ok = k0 + lkey < T;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const size_t o = (size_t)(ld0 + 8 * i) * T + k0 + lkey;
-            kreg[i] = ok ? K[o] : 0.f;
-            vreg[i] = ok ? V[o] : 0.f;
-        }
-    };
-    fetch(0);
-    for (int k0 = 0; k0 < T; k0 += 32) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            Ks[ld0 + 8 * i][lkey] = kreg[i];
-            Vs[ld0 + 8 * i][lkey] = vreg[i];
-        }
-        __syncthreads();
-        if (k0 + 32 < T) fetch(k0 + 32);
-        f32x16 s;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) s[v] = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 32; ++kk) s = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[2 * kk + lh][lr], qreg[kk], s, 0, 0, 0);
-        // s[v] = score of key k0 + (v & 3) + 8 (v >> 2) + 4 lh against query `q` (this lane's column)
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int key = k0 + (v & 3) + 8 * (v >> 2) + 4 * lh;
-            if (key >= T) s[v] = -INFINITY;
-            tmax = fmaxf(tmax, s[v]);
-        }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float mn = fmaxf(m, tmax);              // finite: key k0 < T belongs to this tile
-        const float alpha = expf(m - mn);
-        m = mn;
-        float ps = 0.f;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            s[v] = expf(s[v] - mn);
-            ps += s[v];
-        }
-        l = fmaf(l, alpha, ps);
-#pragma unroll
-        for (int v = 0; v < 16; ++v) { o0[v] *= alpha; o1[v] *= alpha; }
-#pragma unroll
-        for (int st = 0; st < 16; ++st) {
-            const int key = (st & 3) + 8 * (st >> 2) + 4 * lh;
-            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[lr][key], s[st], o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[32 + lr][key], s[st], o1, 0, 0, 0);
-        }
-    }
-    l += __shfl_xor(l, 32, 64);
-    if (q >= T) return;
-    const float inv = 1.f / l;
-    float* dst = out + ((size_t)b * D + h * 64) * T + q;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int d = (v & 3) + 8 * (v >> 2) + 4 * lh;
-        dst[(size_t)d * T] = o0[v] * inv;
-        dst[(size_t)(d + 32) * T] = o1[v] * inv;
-    }
-}
-
 }  // namespace
 
 extern "C" int alm_hubert_conv0_chunks(long long Tout) { return Tout <= 0 ? 0 : (int)((Tout + C0_CHUNK - 1) / C0_CHUNK); }
@@ -371,37 +193,6 @@ extern "C" int alm_hubert_conv0_apply(const float* wave, long long ld_wave, cons
     if (const int rc = conv0_check(B, C, Tin, Tout, ksize, stride, ld_wave)) return rc;
     hipLaunchKernelGGL(conv0_apply_kernel, dim3((unsigned)((Tout + 255) / 256), (C + C0_CG - 1) / C0_CG, B), dim3(256), 0, (hipStream_t)stream, wave,
                        ld_wave, w, reinterpret_cast<const float2*>(stats), gamma, beta, out, C, Tout, ksize, stride);
-    ALM_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int alm_conv1d_valid(const float* x, const float* w, const float* bias, const float* residual, float* out, int B, int Cin, int Cout,
-                                int Tin, int Tout, int ksize, int stride, int pad, int groups, int gelu, void* stream) {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || Tin <= 0 || Tout <= 0 || ksize <= 0 || stride <= 0 || pad < 0 || groups <= 0) return ALM_ERR_BAD_ARG;
-    if (Cin % groups || Cout % groups) return ALM_ERR_BAD_ARG;
-    const long long full = ((long long)Tin + 2LL * pad - ksize) / stride + 1;
-    if ((long long)Tin + 2LL * pad < ksize || Tout > full) return ALM_ERR_BAD_ARG;          // Tout < full drops trailing outputs (SamePad)
-    const long long tiles_y = (long long)((Cout / groups + 63) / 64) * groups;
-    // in-row indices are 32-bit: (Tout + 63) * stride and (Cin / groups) * ksize must fit; rows and batches are offset in 64 bits
-    if (((long long)Tout + 64) * stride + ksize >= (1LL << 31) || (long long)(Cin / groups) * ksize >= (1LL << 31) - 64 || tiles_y > 65535 || B > 65535)
-        return ALM_ERR_UNSUPPORTED;
-    ConvArgs a{x, w, bias, residual, out, Cin, Cout, Tin, Tout, ksize, stride, pad, groups, gelu};
-    const dim3 grid((Tout + 63) / 64, (unsigned)tiles_y, B), block(256);
-    switch (ksize) {
-        case 1: hipLaunchKernelGGL(conv_valid_kernel<1>, grid, block, 0, (hipStream_t)stream, a); break;
-        case 2: hipLaunchKernelGGL(conv_valid_kernel<2>, grid, block, 0, (hipStream_t)stream, a); break;
-        case 3: hipLaunchKernelGGL(conv_valid_kernel<3>, grid, block, 0, (hipStream_t)stream, a); break;
-        case 128: hipLaunchKernelGGL(conv_valid_kernel<128>, grid, block, 0, (hipStream_t)stream, a); break;
-        default: hipLaunchKernelGGL(conv_valid_kernel<0>, grid, block, 0, (hipStream_t)stream, a); break;
-    }
-    ALM_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int alm_mha_attn_fwd(const float* qkv, float* out, int B, int H, int T, int dim_head, float scale, void* stream) {
-    if (B <= 0 || H <= 0 || T <= 0) return ALM_ERR_BAD_ARG;
-    if (dim_head != 64 || B > 65535 || H > 65535) return ALM_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(mha_attn_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, (hipStream_t)stream, qkv, out, H, T, scale);
     ALM_LAUNCH_CHECK();
     return 0;
 }

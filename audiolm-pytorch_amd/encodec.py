@@ -24,9 +24,9 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
+from .frozen import F32, FrozenModel, load_weights
 from .resample import resample
 
-F32 = torch.float32
 _IGNORED = re.compile(r'^quantizer\.layers\.\d+\.codebook\.(inited|cluster_size|embed_avg)$')
 _CONFIG = dict(num_filters=32, upsampling_ratios=(8, 5, 4, 2), hidden_size=128, codebook_size=1024, num_lstm_layers=2, kernel_size=7, last_kernel_size=7,
                residual_kernel_size=3, num_residual_layers=1, dilation_growth_rate=2, compress=2, use_conv_shortcut=True, sampling_rate=24000)
@@ -117,13 +117,10 @@ def _load_file(path):
     path = str(path)
     if not os.path.exists(path):
         raise FileNotFoundError(f'checkpoint_path {path} does not exist (a local file is required: hub names are never resolved)')
-    if path.endswith('.safetensors'):
-        try:
-            from safetensors.torch import load_file
-        except ImportError as e:
-            raise NotImplementedError('.safetensors checkpoints need the `safetensors` package, which is not installed: pass a torch.load-able file') from e
-        return load_file(path)
-    sd = torch.load(path, map_location='cpu', weights_only=True)
+    try:
+        sd = load_weights(path)
+    except ImportError as e:
+        raise NotImplementedError('.safetensors checkpoints need the `safetensors` package, which is not installed: pass a torch.load-able file') from e
     return sd['state_dict'] if isinstance(sd, dict) and 'state_dict' in sd and isinstance(sd['state_dict'], dict) else sd
 
 
@@ -147,11 +144,7 @@ def lstm_skip(image, x):
     return ops.lstm_seq(xproj, w_ih, w_hh, bias, skip=xs, out_bct=True)
 
 
-class _Node(nn.Module):
-    """a named slot of the parameter tree (never called: the kernels read the tensors)"""
-
-
-class EncodecWrapper(nn.Module):
+class EncodecWrapper(FrozenModel):
     """Positional order and members of the reference class (encodec.py:37-43).  `num_quantizers` is accepted and, as in the reference, replaced by what
     `bandwidth` selects.  Weights: keyword-only `checkpoint_path` (a torch.load-able state dict, or .safetensors where that package is installed) or
     `EncodecWrapper.from_state_dict`.  `config`: num_filters, upsampling_ratios, hidden_size, codebook_size, num_lstm_layers, kernel_size, last_kernel_size,
@@ -214,47 +207,26 @@ class EncodecWrapper(nn.Module):
         books = sorted(int(k.split('.')[2]) for k in sd if re.match(r'^quantizer\.layers\.\d+\.codebook\.embed$', k))
         if books != list(range(len(books))) or len(books) < self.num_quantizers:
             raise KeyError(f'bandwidth {self.bandwidth} needs codebooks 0 .. {self.num_quantizers - 1}; the state dict holds {books}')
-        missing = [n for n in names if n not in sd]
-        if missing:
-            raise KeyError(f'the state dict lacks {len(missing)} entries of the EnCodec model: {missing[:6]}' + (' ...' if len(missing) > 6 else ''))
-        extra = [k for k in sd if k not in names and not k.startswith('quantizer.layers.')]
-        if extra:
-            raise KeyError(f'unexpected entries in the state dict: {extra[:6]}')
+        self._adopt(names, sd, 'the EnCodec model', lambda k: k.startswith('quantizer.layers.'))
         for n, shape in shapes.items():
             if tuple(sd[n].shape) != shape:
                 raise ValueError(f'{n}: shape {tuple(sd[n].shape)} does not match the configuration ({shape})')
-        for n in names:
-            self._slot(n).register_parameter(n.rsplit('.', 1)[1], nn.Parameter(sd[n].detach().to(F32).clone().contiguous(), requires_grad=False))
         for q in books:
             E = sd[f'quantizer.layers.{q}.codebook.embed']
             if tuple(E.shape) != (cfg['codebook_size'], cfg['hidden_size']):
                 raise ValueError(f"codebook {q}: shape {tuple(E.shape)} does not match ({cfg['codebook_size']}, {cfg['hidden_size']})")
             self._slot(f'quantizer.layers.{q}.codebook.embed').register_buffer('embed', E.detach().to(F32).clone().contiguous())
         self.num_codebooks = len(books)
-        self._images = None
-        self.register_load_state_dict_post_hook(lambda module, incompatible: setattr(module, '_images', None))
         self.eval()
-
-    def _slot(self, name):
-        node = self
-        for part in name.split('.')[:-1]:
-            if part not in node._modules:
-                node.add_module(part, _Node())
-            node = node._modules[part]
-        return node
-
-    def _apply(self, fn, *args, **kwargs):
-        self._images = None
-        return super()._apply(fn, *args, **kwargs)
 
     # ---- derived tensors, computed once per load / device move ------------------------------------------------------------------------------------
 
     def _prepare(self):
         """weight norm folded (w = g v / |v|, the norm over every axis but 0 -- for the transposed conv's [Cin, Cout, k] weight axis 0 is the INPUT
         channel, torch.nn.utils.weight_norm's default dim), the MFMA images of the conv weights and of the codebooks, the LSTM weights stacked"""
-        if self._images is not None:
-            return self._images
-        cfg, t = self.config, dict(self.named_parameters())
+        if 'images' in self._cache:
+            return self._cache['images']
+        cfg, t = self.config, self._params()
         im = {}
         tr = {f'decoder.layers.{e[1]}': e for e in _layout(cfg)[1] if e[0] == 'convtr'}
         for p in _conv_prefixes(cfg):
@@ -274,7 +246,7 @@ class EncodecWrapper(nn.Module):
         b = dict(self.named_buffers())
         E = torch.stack([b[f'quantizer.layers.{q}.codebook.embed'] for q in range(self.num_codebooks)]).contiguous()
         im['codebooks'] = (E, E[:self.num_quantizers].contiguous()) + ops.rvq_pack(E[:self.num_quantizers].contiguous())
-        self._images = im
+        self._cache['images'] = im
         return im
 
     # ---- the layers -----------------------------------------------------------------------------------------------------------------------------

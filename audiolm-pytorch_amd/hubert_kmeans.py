@@ -2,7 +2,7 @@
 
 The reference runs a fairseq HuBERT-base feature model (`model(wav, features_only=True, mask=False, output_layer=L)['x']`) and assigns each 20 ms
 frame to its nearest k-means centre (`(-cdist(embed, centres)).argmax(-1)`).  Here the model is restated on the project's fp32 kernels
-(csrc/hubert.hip, csrc/codec.hip), in the codec's [B][C][T] layout:
+(csrc/hubert.hip, csrc/dense_f32.hip, csrc/codec.hip), in the codec's [B][C][T] layout:
 
   wave [B, T] -> conv0 (1 -> C, k 10, stride 5) + GroupNorm(C, C) over time + GELU     alm_hubert_conv0_stats / _apply
               -> 6 bias-less convs (k 3 3 3 3 2 2, stride 2) + GELU                       alm_conv1d_valid
@@ -25,10 +25,10 @@ import torch
 from torch import nn
 
 from . import ops
+from .frozen import F32, FrozenModel, load_weights
 from .resample import resample
 from .soundstream import curtail_to_multiple
 
-F32 = torch.float32
 BASE_CONV_LAYERS = '[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2'
 _IGNORED = re.compile(r'^(mask_emb$|final_proj\.|label_embs_concat$|target_glu\.)')
 _LAYER_KEYS = [f'{m}.{p}' for m in ('self_attn.q_proj', 'self_attn.k_proj', 'self_attn.v_proj', 'self_attn.out_proj', 'self_attn_layer_norm', 'fc1', 'fc2',
@@ -131,15 +131,7 @@ def frame_count(num_samples, conv_layers=None):
     return n
 
 
-def _refold(module, incompatible_keys):
-    module._fold()
-
-
-class _Node(nn.Module):
-    """a named slot of the parameter tree (never called: the kernels read the tensors)"""
-
-
-class HubertWithKmeans(nn.Module):
+class HubertWithKmeans(FrozenModel):
     """Positional order, defaults and members of the reference class (hubert_kmeans.py:43-95).  `checkpoint_path`: torch.load-able, either a fairseq
     checkpoint ({'model': state dict, 'cfg': {'model': ..., 'task': ...}} or {'model': ..., 'args': Namespace}) or a bare state dict;
     `kmeans_path`: joblib file of an object with `cluster_centers_`, or a .pt / .npy file holding the (clusters, dim) array."""
@@ -203,22 +195,10 @@ class HubertWithKmeans(nn.Module):
                   'post_extract_proj.weight', 'post_extract_proj.bias', 'encoder.pos_conv.0.bias', 'encoder.pos_conv.0.weight_g',
                   'encoder.pos_conv.0.weight_v', 'encoder.layer_norm.weight', 'encoder.layer_norm.bias']
         names += [f'encoder.layers.{i}.{k}' for i in range(self.output_layer) for k in _LAYER_KEYS]
-        missing = [n for n in names if n not in state_dict]
-        if missing:
-            raise KeyError(f'the state dict lacks {len(missing)} entries of a {self.output_layer}-layer HuBERT: {missing[:6]}' + (' ...' if len(missing) > 6 else ''))
-        extra = [k for k in state_dict if k not in names and not _IGNORED.match(k) and not re.match(r'encoder\.layers\.(\d+)\.', k)]
-        if extra:
-            raise KeyError(f'unexpected entries in the state dict: {extra[:6]}')
-        for n in names:                                            # layers at index output_layer and above are not kept
-            node = self
-            *path, leaf = n.split('.')
-            for part in path:
-                if part not in node._modules:
-                    node.add_module(part, _Node())
-                node = node._modules[part]
-            node.register_parameter(leaf, nn.Parameter(state_dict[n].detach().to(F32).clone().contiguous(), requires_grad=False))
+        # layers at index output_layer and above are not kept
+        self._adopt(names, state_dict, f'a {self.output_layer}-layer HuBERT', lambda k: _IGNORED.match(k) or re.match(r'encoder\.layers\.(\d+)\.', k))
 
-        sd = dict(self.named_parameters())
+        sd = self._params()
         C_prev = 1
         for i, (c, k, s) in enumerate(self.conv_layers):
             w = sd[f'feature_extractor.conv_layers.{i}.0.weight']
@@ -242,24 +222,18 @@ class HubertWithKmeans(nn.Module):
             raise ValueError(f'cluster centres must be (clusters, {D}), got {tuple(centres.shape)}')
         self.register_buffer('cluster_centers', centres.clone())
         self._fold()
-        self.register_load_state_dict_post_hook(_refold)
         self.eval()
 
     def _fold(self):
         """derived tensors, computed once at load: the positional conv's weight norm folded (w = g v / |v|, the norm over all but the tap axis,
-        torch.nn.utils.weight_norm(dim=2)), the q | k | v projections stacked for one launch, the MFMA image of the centres"""
-        p = dict(self.named_parameters())
+        torch.nn.utils.weight_norm(dim=2)), the q | k | v projections stacked for one launch"""
+        p = self._params()
         g, v = p['encoder.pos_conv.0.weight_g'], p['encoder.pos_conv.0.weight_v']
         self.register_buffer('_pos_w', (v * (g / v.norm(dim=(0, 1), keepdim=True))).contiguous(), persistent=False)
         for i in range(self.output_layer):
             pre = f'encoder.layers.{i}.self_attn.'
             self.register_buffer(f'_qkv_w{i}', torch.cat([p[pre + f'{n}_proj.weight'] for n in 'qkv']).unsqueeze(-1).contiguous(), persistent=False)
             self.register_buffer(f'_qkv_b{i}', torch.cat([p[pre + f'{n}_proj.bias'] for n in 'qkv']).contiguous(), persistent=False)
-        self._centre_image = None
-
-    def _apply(self, fn, *args, **kwargs):
-        self._centre_image = None
-        return super()._apply(fn, *args, **kwargs)
 
     @property
     def groups(self):
@@ -286,7 +260,7 @@ class HubertWithKmeans(nn.Module):
         """wave (b, t) at target_sample_hz -> the output of encoder layer `output_layer`, fp32 (b, n, dim): what fairseq returns as
         model(wav, features_only=True, mask=False, output_layer=L)['x']"""
         self._check(wav_input, padding_mask)
-        p = dict(self.named_parameters())
+        p, lin = self._params(), self._linear
         x = wav_input.to(F32)
         c0, k0, s0 = self.conv_layers[0]
         w0 = p['feature_extractor.conv_layers.0.0.weight'].view(c0, k0)
@@ -295,7 +269,7 @@ class HubertWithKmeans(nn.Module):
         for i, (_, _, s) in enumerate(self.conv_layers[1:], 1):
             x = ops.conv1d_valid(x, p[f'feature_extractor.conv_layers.{i}.0.weight'], stride=s, gelu=True)
         x = ops.layernorm_bct_split(x, p['layer_norm.weight'], p['layer_norm.bias'], eps=1e-5)
-        x = ops.conv1d_valid(x, p['post_extract_proj.weight'].unsqueeze(-1), p['post_extract_proj.bias'])
+        x = ops.conv1d_valid(x, lin('post_extract_proj.weight'), p['post_extract_proj.bias'])
         # pos_conv pads conv_pos // 2 on both sides; SamePad drops the last output of an even kernel; x = x + gelu(.)
         x = ops.conv1d_valid(x, self._pos_w, p['encoder.pos_conv.0.bias'], pad=self.conv_pos // 2, groups=self.conv_pos_groups, gelu=True, residual=x,
                              drop_last=1 if self.conv_pos % 2 == 0 else 0)
@@ -304,10 +278,10 @@ class HubertWithKmeans(nn.Module):
             pre = f'encoder.layers.{i}.'
             qkv = ops.conv1d_valid(x, getattr(self, f'_qkv_w{i}'), getattr(self, f'_qkv_b{i}'))
             a = ops.mha_attn(qkv, self.heads)
-            x = ops.conv1d_valid(a, p[pre + 'self_attn.out_proj.weight'].unsqueeze(-1), p[pre + 'self_attn.out_proj.bias'], residual=x)
+            x = ops.conv1d_valid(a, lin(pre + 'self_attn.out_proj.weight'), p[pre + 'self_attn.out_proj.bias'], residual=x)
             x = ops.layernorm_bct_split(x, p[pre + 'self_attn_layer_norm.weight'], p[pre + 'self_attn_layer_norm.bias'], eps=1e-5)
-            h = ops.conv1d_valid(x, p[pre + 'fc1.weight'].unsqueeze(-1), p[pre + 'fc1.bias'], gelu=True)
-            x = ops.conv1d_valid(h, p[pre + 'fc2.weight'].unsqueeze(-1), p[pre + 'fc2.bias'], residual=x)
+            h = ops.conv1d_valid(x, lin(pre + 'fc1.weight'), p[pre + 'fc1.bias'], gelu=True)
+            x = ops.conv1d_valid(h, lin(pre + 'fc2.weight'), p[pre + 'fc2.bias'], residual=x)
             x = ops.layernorm_bct_split(x, p[pre + 'final_layer_norm.weight'], p[pre + 'final_layer_norm.bias'], eps=1e-5)
         return ops.bct_to_btc(x)
 
@@ -316,9 +290,7 @@ class HubertWithKmeans(nn.Module):
         """fp32 (b, n, dim) -> long (b, n): (-cdist(embed, centres)).argmax(-1), the first index on ties (hubert_kmeans.py:114-116)"""
         b, n, d = embed.shape
         E = self.cluster_centers.unsqueeze(0)
-        if self._centre_image is None:
-            self._centre_image = ops.rvq_pack(E)
-        ids = ops.rvq_encode(embed.reshape(b * n, d), E, *self._centre_image)
+        ids = ops.rvq_encode(embed.reshape(b * n, d), E, *self._cached('centre_image', lambda: ops.rvq_pack(E)))
         return ids.view(b, n)
 
     @torch.no_grad()
@@ -337,7 +309,7 @@ class HubertWithKmeans(nn.Module):
 def _load_centres(path):
     path = str(path)
     if path.endswith('.pt'):
-        c = torch.load(path, map_location='cpu', weights_only=True)
+        c = load_weights(path)
         return c['cluster_centers'] if isinstance(c, dict) else c
     if path.endswith('.npy'):
         import numpy as np

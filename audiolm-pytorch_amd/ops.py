@@ -1119,7 +1119,7 @@ def local_attn(qkv, q_scale, k_scale, cos_t, sin_t, xpos_t, gates, heads, dim_he
     return out
 
 
-# ---- HuBERT feature model (csrc/hubert.hip) ----
+# ---- HuBERT feature model (csrc/hubert.hip; conv1d_valid and mha_attn are the shared fp32 kernels of csrc/dense_f32.hip) ----
 def hubert_conv0_stats(wave, w, stride, eps=1e-5):
     """wave fp32 [B, Tin] (unit element stride), w fp32 [C, k] -> stats fp32 [B, C, 2] = (mean, rstd) over time of conv1d(wave, w, stride), the
     activation never stored (alm_hubert_conv0_stats: shifted sums per chunk, chunks merged in order)."""
@@ -1194,7 +1194,7 @@ def mha_attn(qkv, heads, scale=None, dim_head=64):
     return out
 
 
-# ---- T5 text encoder (csrc/t5.hip): activations fp32 [C, N], N = B * T columns ----
+# ---- T5 text encoder (csrc/t5.hip; t5_attn: csrc/dense_f32.hip): activations fp32 [C, N], N = B * T columns ----
 def t5_embed(ids, table):
     """ids int64 [B, T], table fp32 [vocab, D] -> fp32 [D, B * T] (alm_t5_embed).  An id outside the table is embedded as zeros and raises the
     device error word (see device_error_flag), polled like the other embedding lookups."""

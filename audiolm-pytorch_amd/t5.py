@@ -2,7 +2,7 @@
 
 The reference runs `transformers.T5EncoderModel` in eager torch inside every conditioned training step.  Here the encoder (T5Stack: shared embedding,
 pre-norm blocks of relative-position-biased self-attention and a (gated) feed-forward, final norm) is restated on the project's fp32 kernels
-(csrc/t5.hip, alm_conv1d_valid of csrc/hubert.hip), activations [C][B * T]:
+(csrc/t5.hip; alm_conv1d_valid and the attention: csrc/dense_f32.hip), activations [C][B * T]:
 
   ids [B, T] -> shared[ids]                                                                  alm_t5_embed
              -> L blocks: x += o(attn(q | k | v (norm(x)), bias, mask)); x += wo(gate(wi (norm(x))))   alm_t5_rmsnorm, alm_conv1d_valid (k = 1),
@@ -21,11 +21,10 @@ import os
 import re
 
 import torch
-from torch import nn
 
 from . import ops
+from .frozen import FrozenModel, load_weights
 
-F32 = torch.float32
 MAX_LENGTH = 256
 DEFAULT_T5_NAME = 'google/t5-v1_1-base'
 
@@ -55,15 +54,7 @@ def relative_position_bucket(relative_position, num_buckets=32, max_distance=128
     return relative_buckets + torch.where(is_small, relative_position, relative_position_if_large)
 
 
-def _refold(module, incompatible_keys):
-    module._fold()
-
-
-class _Node(nn.Module):
-    """a named slot of the parameter tree (never called: the kernels read the tensors)"""
-
-
-class T5Encoder(nn.Module):
+class T5Encoder(FrozenModel):
     """`transformers.T5EncoderModel`, frozen, fp32, GPU only.  Build it with from_state_dict / from_pretrained."""
 
     def __init__(self, state_dict, *, num_heads, d_kv=64, feed_forward_proj='gated-gelu', relative_attention_num_buckets=32,
@@ -81,10 +72,9 @@ class T5Encoder(nn.Module):
         self.num_buckets, self.max_distance = int(relative_attention_num_buckets), int(relative_attention_max_distance)
         self.eps = float(layer_norm_epsilon)
 
-        sd = {k: v for k, v in state_dict.items() if not _IGNORED.match(k)}
-        if _ALIAS in sd:
-            alias = sd.pop(_ALIAS)
-            sd.setdefault('shared.weight', alias)
+        sd = state_dict
+        if _ALIAS in sd and 'shared.weight' not in sd:
+            sd = {**sd, 'shared.weight': sd[_ALIAS]}
         layers = {int(m.group(1)) for m in (re.match(r'encoder\.block\.(\d+)\.', k) for k in sd) if m}
         self.num_layers = L = max(layers) + 1 if layers else 0
         ff = ('wi_0', 'wi_1', 'wo') if self.gated else ('wi', 'wo')
@@ -93,23 +83,12 @@ class T5Encoder(nn.Module):
             names += [f'encoder.block.{i}.layer.0.SelfAttention.{n}.weight' for n in 'qkvo']
             names += [f'encoder.block.{i}.layer.{j}.layer_norm.weight' for j in (0, 1)]
             names += [f'encoder.block.{i}.layer.1.DenseReluDense.{n}.weight' for n in ff]
-        missing = [n for n in names if n not in sd]
-        if missing or L == 0:
-            raise KeyError(f'the state dict lacks {len(missing)} entries of a {L}-block {feed_forward_proj} T5 encoder: {missing[:6]}'
-                           + (' ...' if len(missing) > 6 else ''))
-        extra = [k for k in sd if k not in names]
-        if extra:
-            raise KeyError(f'unexpected entries in the state dict: {extra[:6]}')
-        for n in names:
-            node = self
-            *path, leaf = n.split('.')
-            for part in path:
-                if part not in node._modules:
-                    node.add_module(part, _Node())
-                node = node._modules[part]
-            node.register_parameter(leaf, nn.Parameter(sd[n].detach().to(F32).clone().contiguous(), requires_grad=False))
+        what = f'a {L}-block {feed_forward_proj} T5 encoder'
+        if L == 0:
+            raise self._lacks([n for n in names if n not in sd], what)
+        self._adopt(names, sd, what, lambda k: _IGNORED.match(k) or k == _ALIAS)
 
-        p = dict(self.named_parameters())
+        p = self._params()
         self.vocab_size, self.d_model = p['shared.weight'].shape
         inner = self.num_heads * 64
         if tuple(p[_BIAS_KEY].shape) != (self.num_buckets, self.num_heads):
@@ -125,7 +104,6 @@ class T5Encoder(nn.Module):
                 if tuple(p[pre + k].shape) != shape:
                     raise ValueError(f'{pre + k} is {tuple(p[pre + k].shape)}, expected {shape} ({self.num_heads} heads of 64)')
         self._fold()
-        self.register_load_state_dict_post_hook(_refold)
         self.eval()
 
     @classmethod
@@ -149,14 +127,10 @@ class T5Encoder(nn.Module):
                                     'model.safetensors / pytorch_model.bin) and never resolves a hub name')
         with open(os.path.join(directory, 'config.json')) as fh:
             cfg = json.load(fh)
-        st, pt = os.path.join(directory, 'model.safetensors'), os.path.join(directory, 'pytorch_model.bin')
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st, device='cpu')
-        elif os.path.exists(pt):
-            sd = torch.load(pt, map_location='cpu', weights_only=True)
-        else:
+        files = [f for f in (os.path.join(directory, n) for n in ('model.safetensors', 'pytorch_model.bin')) if os.path.exists(f)]
+        if not files:
             raise FileNotFoundError(f'{directory!r} holds neither model.safetensors nor pytorch_model.bin')
+        sd = load_weights(files[0])
         ffp = cfg.get('feed_forward_proj', 'relu')
         return cls(sd, num_heads=cfg['num_heads'], d_kv=cfg.get('d_kv', 64), feed_forward_proj=ffp,
                    relative_attention_num_buckets=cfg.get('relative_attention_num_buckets', 32),
@@ -166,29 +140,23 @@ class T5Encoder(nn.Module):
     def _fold(self):
         """derived tensors, computed at load and after load_state_dict: q | k | v and wi_0 | wi_1 stacked for one launch each, every Linear weight
         in the [Cout, Cin, 1] form of alm_conv1d_valid; the per-length bias tables are rebuilt on demand"""
-        p = dict(self.named_parameters())
+        p = self._params()
         for i in range(self.num_layers):
             att, ffn = f'encoder.block.{i}.layer.0.SelfAttention.', f'encoder.block.{i}.layer.1.DenseReluDense.'
             self.register_buffer(f'_qkv_w{i}', torch.cat([p[att + f'{n}.weight'] for n in 'qkv']).unsqueeze(-1).contiguous(), persistent=False)
             wi = torch.cat([p[ffn + 'wi_0.weight'], p[ffn + 'wi_1.weight']]) if self.gated else p[ffn + 'wi.weight']
             self.register_buffer(f'_wi_w{i}', wi.unsqueeze(-1).contiguous(), persistent=False)
-        self._bias_tables = {}
-
-    def _apply(self, fn, *args, **kwargs):
-        self._bias_tables = {}
-        return super()._apply(fn, *args, **kwargs)
 
     def bias_table(self, T, device=None):
         """fp32 [H, 2 T - 1]: entry [h][j - i + T - 1] = relative_attention_bias[bucket(j - i)][h], the whole of T5's position bias for sequences of
         T tokens (it depends on (h, j - i) only).  Built once per (T, device) and kept."""
         w = self.get_parameter(_BIAS_KEY)
         device = w.device if device is None else torch.device(device)
-        key = (int(T), device.type, device.index)
-        tbl = self._bias_tables.get(key)
-        if tbl is None:
+
+        def build():
             bucket = relative_position_bucket(torch.arange(-(T - 1), T, dtype=torch.long), self.num_buckets, self.max_distance)
-            tbl = self._bias_tables[key] = w.detach().to(device)[bucket.to(device)].t().contiguous()
-        return tbl
+            return w.detach().to(device)[bucket.to(device)].t().contiguous()
+        return self._cached(('bias_table', int(T), device.type, device.index), build)
 
     @torch.no_grad()
     def forward(self, input_ids, attention_mask=None):
@@ -206,7 +174,7 @@ class T5Encoder(nn.Module):
             if tuple(attention_mask.shape) != (B, T):
                 raise ValueError(f'attention_mask {tuple(attention_mask.shape)} does not match input_ids {(B, T)}')
             mask = (attention_mask.to(device) != 0).to(torch.uint8).contiguous()
-        p = dict(self.named_parameters())
+        p, w1 = self._params(), self._linear
         bias = self.bias_table(T, device)
         lin = lambda t, w, res=None: ops.conv1d_valid(t.unsqueeze(0), w, residual=None if res is None else res.unsqueeze(0))[0]      # noqa: E731
         x = ops.t5_embed(input_ids.to(torch.long).contiguous(), p['shared.weight'])
@@ -214,10 +182,10 @@ class T5Encoder(nn.Module):
             pre = f'encoder.block.{i}.layer.'
             h = ops.t5_rmsnorm(x, p[pre + '0.layer_norm.weight'], self.eps)
             a = ops.t5_attn(lin(h, getattr(self, f'_qkv_w{i}')), bias, mask, B, self.num_heads)
-            x = lin(a, p[pre + '0.SelfAttention.o.weight'].unsqueeze(-1), x)
+            x = lin(a, w1(pre + '0.SelfAttention.o.weight'), x)
             h = ops.t5_rmsnorm(x, p[pre + '1.layer_norm.weight'], self.eps)
             g = ops.t5_gate(lin(h, getattr(self, f'_wi_w{i}')), self.gated)
-            x = lin(g, p[pre + '1.DenseReluDense.wo.weight'].unsqueeze(-1), x)
+            x = lin(g, w1(pre + '1.DenseReluDense.wo.weight'), x)
         out = ops.t5_rmsnorm(x, p['encoder.final_layer_norm.weight'], self.eps, mask=None if mask is None else mask.view(-1), transpose_out=True)
         return out.view(B, T, self.d_model)
 

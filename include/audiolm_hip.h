@@ -418,7 +418,8 @@ int alm_hubert_conv0_stats(const float* wave, long long ld_wave, const float* w,
                            long long Tout, int ksize, int stride, float eps, void* stream);
 int alm_hubert_conv0_apply(const float* wave, long long ld_wave, const float* w, const float* stats, const float* gamma, const float* beta,
                            float* out, int B, int C, long long Tin, long long Tout, int ksize, int stride, void* stream);
-/* conv1d with symmetric zero padding `pad` and `groups` (wav2vec2.py conv layers 1..6: pad 0, GELU; TransformerEncoder.pos_conv + SamePad + GELU
+/* csrc/dense_f32.hip, shared with the T5 encoder and EnCodec's LSTM projection.
+ * conv1d with symmetric zero padding `pad` and `groups` (wav2vec2.py conv layers 1..6: pad 0, GELU; TransformerEncoder.pos_conv + SamePad + GELU
  * + the residual add of extract_features: groups 16, k 128, pad 64, Tout = Tin; the nn.Linear layers: k 1): x [B][Cin][Tin], w [Cout][Cin / groups]
  * [ksize] (torch's layout, unpacked), out [B][Cout][Tout] = (gelu ? erf-GELU : id)(conv + bias) + residual; bias / residual may be NULL.
  * Tout <= (Tin + 2 pad - ksize) / stride + 1 (a smaller Tout drops trailing outputs), else ALM_ERR_BAD_ARG.  Batch and channel-row offsets are
@@ -428,11 +429,13 @@ int alm_conv1d_valid(const float* x, const float* w, const float* bias, const fl
 /* nn.LayerNorm over the channel axis of [B][C][T] (wav2vec2.py: layer_norm, encoder.layer_norm, self_attn_layer_norm, final_layer_norm), the
  * arguments of alm_layernorm_bct; 32 channel slices per time step and a two-pass variance, for sequences too short to fill the chip one thread per t. */
 int alm_layernorm_bct_split(const float* x, const float* gamma, const float* beta, float* out, int B, int C, int T, float eps, void* stream);
-/* fairseq MultiheadAttention (self-attention, no mask, eval): qkv [B][3 H dim_head][T] (q | k | v channel blocks) -> out [B][H dim_head][T] =
+/* csrc/dense_f32.hip.  fairseq MultiheadAttention (self-attention, no mask, eval):
+ * qkv [B][3 H dim_head][T] (q | k | v channel blocks) -> out [B][H dim_head][T] =
  * softmax((scale q) . k) v per head, flash style (online softmax, no score matrix in memory).  dim_head == 64, else ALM_ERR_UNSUPPORTED. */
 int alm_mha_attn_fwd(const float* qkv, float* out, int B, int H, int T, int dim_head, float scale, void* stream);
 
-/* ---- T5 text encoder (csrc/t5.hip): transformers T5Stack (encoder) as the reference's t5.py:68-110 calls it, restated in tests/t5_restated.py.
+/* ---- T5 text encoder (csrc/t5.hip; _attn_fwd: csrc/dense_f32.hip): transformers T5Stack (encoder) as the reference's t5.py:68-110 calls it,
+ * restated in tests/t5_restated.py.
  * fp32, inference only.  Activations are [C][N], N = B T columns (sample b = columns b T .. b T + T - 1); the bias-less Linear layers are
  * alm_conv1d_valid with B = 1, ksize = 1, Tin = N.
  * _embed: ids int64 [N] -> out [D][N] = table[ids[n]][c], table [vocab][D].  An id outside [0, vocab) is not dereferenced: zero column and

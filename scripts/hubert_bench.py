@@ -1,4 +1,4 @@
-"""Device time of audiolm_pytorch_amd.HubertWithKmeans (csrc/hubert.hip) at 8 x 10 s and 8 x 30 s of 16 kHz audio, HuBERT-base, 9 layers, 500 centres:
+"""Device time of audiolm_pytorch_amd.HubertWithKmeans (csrc/hubert.hip, csrc/dense_f32.hip) at 8 x 10 s and 8 x 30 s of 16 kHz audio, HuBERT-base, 9 layers, 500 centres:
 per kernel and end to end, beside the restated module (tests/hubert_restated.py) in fp32 through ATen on the same GPU.  The two end-to-end runs alternate
 inside one process (native, ATen, native, ...), so that both see the same clocks and the same neighbours.  For the conv and GEMM kernels the achieved
 FLOP/s is given as a fraction of the fp32 matrix peak (157.3 TFLOP/s, v_mfma_f32_32x32x2_f32); operation counts come from the shapes.

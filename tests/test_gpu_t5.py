@@ -231,6 +231,26 @@ def test_attention_without_a_mask_and_unsupported_head_width():
         ops.t5_attn(rnd(3 * 2 * 128, 8).to(dev()), rnd(2, 7).to(dev()), None, 2, 2, dim_head=128)
 
 
+@pytest.mark.parametrize('T', [1, 32, 33, 129])
+def test_biased_attention_with_nothing_to_add_is_the_plain_kernel(T):
+    """the two attention entry points are one kernel (csrc/dense_f32.hip): with a zero bias table and no key masked, t5_attn gives the bits of
+    mha_attn.  Q times 0.125 is exact on the host (a power of two), so every matrix-core operand is the same; s + 0.0 changes at most the sign of a
+    zero score, which cannot reach exp(s - max); no tile is skipped and every row sum is positive.  One tile, a tile boundary, a ragged tail,
+    more than one 128-query block."""
+    B, H = 2, 2
+    D = H * 64
+    qkv = rnd(B, 3 * D, T, seed=T)
+    ops = OPS()
+    plain = ops.mha_attn(qkv.to(dev()), H, scale=0.125)
+    scaled = qkv.clone()
+    scaled[:, :D] *= 0.125
+    cn = scaled.permute(1, 0, 2).reshape(3 * D, B * T).contiguous().to(dev())
+    zeros = torch.zeros(H, 2 * T - 1, device=dev())
+    for mask in (None, torch.ones(B, T, dtype=torch.uint8, device=dev())):
+        got = ops.t5_attn(cn, zeros, mask, B, H).view(D, B, T).permute(1, 0, 2)
+        assert torch.equal(got, plain), (T, mask is None)
+
+
 # ---------------------------------------------------------------- whole model
 def rel_l2(got, want, valid):
     return float(((got.double() - want).norm(dim=-1)[valid] / want.norm(dim=-1)[valid]).max())
