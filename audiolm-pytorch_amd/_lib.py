@@ -114,6 +114,11 @@ SIGNATURES = {
     'alm_rvq_pack': [_P, _P, _P, _I, _I, _I, _P],
     'alm_rvq_encode': [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P],
     'alm_bct_to_btc': [_P, _P, _I, _I, _I, _P],
+    'alm_conv1d_wgrad_chunk': [_I, _I],
+    'alm_conv1d_wgrad_ws_floats': [_I, _I, _I, _I, _I],
+    'alm_conv1d_dgrad': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_conv1d_wgrad': [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_phase_deinterleave': [_P, _P, _I, _I, _I, _I, _P],
     'alm_resample_sinc': [_P, _L, _P, _L, _P, _I, _L, _L, _L, _I, _I, _I, _P],
     'alm_resample_sinc_bwd': [_P, _L, _P, _L, _P, _I, _L, _L, _L, _I, _I, _I, _P],
     'alm_hubert_conv0_chunks': [_L],

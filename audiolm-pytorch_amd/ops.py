@@ -1053,6 +1053,64 @@ def bct_to_btc(x):
     return out
 
 
+# ---- backward of the codec's conv stacks (csrc/codec_bwd.hip), exact fp32, no atomics
+
+def conv1d_pack_t(w):
+    """nn.Conv1d weight fp32 [Cout, Cin, k] -> the image alm_conv1d_dgrad reads: alm_conv1d_pack of the transposed weight, [k][Cout_pad][Cin_pad]."""
+    _chk(w, F32)
+    return conv1d_pack(w.transpose(0, 1).contiguous())
+
+
+def conv1d_dgrad(g, y, wt, Cin, Tin, ksize, *, stride=1, dilation=1, zero_pad=False, residual=None):
+    """g fp32 [B, Cout, Tout] (= dL/dout; times ELU'(y) when the saved post-ELU output y is given) -> dL/dx fp32 [B, Cin, Tin] of conv1d_causal,
+    reflect fold included (+ residual [B, Cin, Tin]).  wt: conv1d_pack_t image."""
+    _chk(g, F32), _chk(wt, F32)
+    B, Cout, Tout = g.shape
+    assert g.is_contiguous() and Tout == (Tin - stride) // stride + 1
+    if y is not None:
+        _chk(y, F32)
+        assert y.shape == g.shape and y.is_contiguous()
+    dx = _new((B, Cin, Tin), dtype=F32, device=g.device)
+    if residual is not None:
+        _chk(residual, F32)
+        assert residual.shape == dx.shape and residual.is_contiguous()
+    _lib.call('alm_conv1d_dgrad', g.data_ptr(), _p(y), wt.data_ptr(), _p(residual), dx.data_ptr(), B, Cin, Cout, Tin, ksize, stride, dilation,
+              int(zero_pad), _st())
+    return dx
+
+
+def conv1d_wgrad(g, y, x, ksize, *, stride=1, dilation=1, zero_pad=False):
+    """g fp32 [B, Cout, Tout] (times ELU'(y) when y is given), x fp32 [B, Cin, Tin] -> (dW fp32 [Cout, Cin, k], db fp32 [Cout]) of conv1d_causal;
+    per-chunk partials in a workspace of alm_conv1d_wgrad_ws_floats floats, summed in chunk order."""
+    _chk(g, F32), _chk(x, F32)
+    B, Cout, Tout = g.shape
+    _, Cin, Tin = x.shape
+    assert g.is_contiguous() and x.is_contiguous() and x.shape[0] == B and Tout == (Tin - stride) // stride + 1
+    if y is not None:
+        _chk(y, F32)
+        assert y.shape == g.shape and y.is_contiguous()
+    n = _lib.query('alm_conv1d_wgrad_ws_floats', B, Cin, Cout, Tout, ksize)
+    if n < 0:
+        raise _lib.AlmError('conv1d_wgrad: the partial-sum workspace exceeds 2^31 floats')
+    ws = _new((n,), dtype=F32, device=g.device)
+    dw = _new((Cout, Cin, ksize), dtype=F32, device=g.device)
+    db = _new((Cout,), dtype=F32, device=g.device)
+    _lib.call('alm_conv1d_wgrad', g.data_ptr(), _p(y), x.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), n, B, Cin, Cout, Tin, ksize, stride,
+              dilation, int(zero_pad), _st())
+    return dw, db
+
+
+def phase_deinterleave(g, Cout, s):
+    """g fp32 [B, Cout, n * s] -> [B, s * Cout, n] (phase-major channels): the adjoint of phase_interleave."""
+    _chk(g, F32)
+    B, C, Ts = g.shape
+    assert C == Cout and Ts % s == 0 and g.is_contiguous()
+    n = Ts // s
+    y = _new((B, s * Cout, n), dtype=F32, device=g.device)
+    _lib.call('alm_phase_deinterleave', g.data_ptr(), y.data_ptr(), B, Cout, s, n, _st())
+    return y
+
+
 def _rows(x):
     """fp32 [R, L] with unit element stride -> (tensor, row stride); copies only when the rows are not evenly strided"""
     if x.stride(-1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):

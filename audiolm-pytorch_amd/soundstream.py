@@ -3,7 +3,9 @@
 return_codes_only=True)` -- the causal-conv encoder (soundstream.py:332-380, 519-531) and the eval-mode forward of the grouped residual VQ
 (soundstream.py:592-607, :840) -- and `decode_from_codebook_indices` / `decode` (soundstream.py:691-709: code lookup, transposed-conv
 decoder :347-360, 382-395, 615-627) run on the MI355X kernels of csrc/codec.hip (exact-fp32 MFMA).  Everything else the reference class
-does (discriminators, losses, training of the codec, LFQ / FSQ quantizers) is out of scope and raises.
+does (discriminators, losses, train-mode RVQ, LFQ / FSQ quantizers) is out of scope and raises.  The conv encoder / decoder are
+differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
+build a graph over the backward kernels of csrc/codec_bwd.hip (codec_bwd.py; use_local_attn=True raises there: no LocalTransformer backward).
 `encoder_attn` / `decoder_attn` (soundstream.py:397-440, 545, 613): local-attention's LocalMHA + FeedForward (third-party source, not vendored:
 restated, parity unpinned -- oracle/local_attention_restated.py) run in the codec's [B, C, T] layout: LayerNorm / windowed causal attention with
 qk-l2norm, rotary + xpos and per-head value gates / GEGLU are csrc/local_attn.hip, the Linear layers are k = 1 convs on the exact-fp32 MFMA kernel.
@@ -28,7 +30,7 @@ from itertools import cycle
 import torch
 from torch import nn
 
-from . import core, ops
+from . import codec_bwd, core, ops
 from .resample import resample
 
 F32 = torch.float32
@@ -47,6 +49,7 @@ class CausalConv1d(nn.Module):                                   # soundstream.p
         self.causal_padding = self.dilation * (kernel_size - 1) + (1 - self.stride)
         self.conv = nn.Conv1d(chan_in, chan_out, kernel_size, **kwargs)
         self._packed = None
+        self._packed_t = codec_bwd._ImageCache()                  # transposed image for the input gradient (training mode only)
 
     def packed(self):
         w = self.conv.weight
@@ -59,8 +62,14 @@ class CausalConv1d(nn.Module):                                   # soundstream.p
         return ops.conv1d_causal(x, self.packed(), self.conv.bias.detach(), self.conv.out_channels, self.kernel_size, stride=self.stride,
                                  dilation=self.dilation, elu=elu, residual=residual)
 
+    def call(self, x, *, elu=False):
+        """run(), or its autograd Function in training mode with grad mode on and something that requires grad"""
+        if codec_bwd.wants_grad(self, x):
+            return codec_bwd.CausalConv1dFn.apply(x, self.conv.weight, self.conv.bias, self, elu)
+        return self.run(x, elu=elu)
+
     def forward(self, x):
-        return self.run(x)
+        return self.call(x)
 
 
 class CausalConvTranspose1d(nn.Module):                          # soundstream.py:347-360
@@ -76,6 +85,7 @@ class CausalConvTranspose1d(nn.Module):                          # soundstream.p
         self.padding = kernel_size - 1
         self.conv = nn.ConvTranspose1d(chan_in, chan_out, kernel_size, stride)
         self._packed = None
+        self._packed_t = codec_bwd._ImageCache()
 
     def packed(self):
         w, b = self.conv.weight, self.conv.bias
@@ -90,11 +100,27 @@ class CausalConvTranspose1d(nn.Module):                          # soundstream.p
             self._packed = (ver, ops.conv1d_pack(w2), b.detach().to(F32).repeat(s).contiguous())
         return self._packed[1], self._packed[2]
 
-    def forward(self, x):
+    def _w2(self):
+        """the weight in the k = 2 conv form W2[(r, co), ci, tap]: tap 0 <- x[q - 1] uses w[ci, co, r + s]; tap 1 <- x[q] uses w[ci, co, r]"""
+        s = self.upsample_factor
+        cin, cout, _ = self.conv.weight.shape
+        wd = self.conv.weight.detach().to(F32)
+        return torch.stack((wd[:, :, s:], wd[:, :, :s]), dim=-1).permute(2, 1, 0, 3).reshape(s * cout, cin, 2).contiguous()
+
+    def packed_t(self):
+        """transposed image of the k = 2 form for the input gradient (alm_conv1d_dgrad), per weight version"""
+        return self._packed_t.get((self.conv.weight,), lambda: ops.conv1d_pack_t(self._w2()))
+
+    def run(self, x):
         wp, b2 = self.packed()
         s, cout = self.upsample_factor, self.conv.out_channels
         y = ops.conv1d_causal(x, wp, b2, s * cout, 2, zero_pad=True)
         return ops.phase_interleave(y, cout, s)
+
+    def forward(self, x):
+        if codec_bwd.wants_grad(self, x):
+            return codec_bwd.CausalConvTranspose1dFn.apply(x, self.conv.weight, self.conv.bias, self)
+        return self.run(x)
 
 
 class _ResidualFn(nn.Module):
@@ -107,6 +133,8 @@ class _ResidualFn(nn.Module):
 
     def forward(self, x):                                        # soundstream.py:362-369: ELU(conv1(ELU(conv7(x)))) + x
         c7, c1 = self.fn[0], self.fn[2]
+        if codec_bwd.wants_grad(self, x):                        # two launches + the skip add, h and the pre-residual output saved (bitwise the fused result)
+            return codec_bwd.ResidualUnitFn.apply(x, c7.conv.weight, c7.conv.bias, c1.conv.weight, c1.conv.bias, self)
         if FUSE_RESUNIT and ops.resunit_supported(x.shape[1]) and c7.dilation * (c7.kernel_size - 1) < x.shape[2]:
             # one launch, the intermediate in registers (alm_resunit_causal: bitwise equal to the two launches below)
             return ops.resunit_causal(x, c7.packed(), c7.conv.bias.detach(), c1.packed(), c1.conv.bias.detach(), c7.kernel_size, c7.dilation)
@@ -399,15 +427,19 @@ class SoundStream(nn.Module):
         if not x.is_cuda:
             raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
         h = x.to(F32).contiguous()
+        grad = codec_bwd.wants_grad(self.encoder, h)
+        if grad and self.encoder_attn is not None:
+            raise NotImplementedError('training-mode SoundStream with use_local_attn=True needs the LocalTransformer backward, which is not implemented '
+                                      '(construct with use_local_attn=False, or call eval())')
         for layer in self.encoder:
             if isinstance(layer, CausalConv1d):
-                h = layer.run(h)
+                h = layer.call(h)
             else:
                 for sub in layer:
-                    h = sub(h) if isinstance(sub, _ResidualFn) else sub.run(h)
+                    h = sub(h) if isinstance(sub, _ResidualFn) else sub.call(h)
         if self.encoder_attn is not None:                        # :830-833 ('b c n -> b n c' first there; here the layout is kept)
             h = self.encoder_attn.run_bct(h)
-        return ops.bct_to_btc(h)
+        return codec_bwd.BctToBtcFn.apply(h) if h.requires_grad else ops.bct_to_btc(h)
 
     @torch.no_grad()
     def tokenize(self, audio):                                   # soundstream.py:797-800
@@ -436,7 +468,6 @@ class SoundStream(nn.Module):
         recon = self.decode(quantized)                           # :857-866, unpack(recon_x, ps, '* c n')
         return recon.reshape(*lead, recon.shape[-2], recon.shape[-1])
 
-    @torch.no_grad()
     def decode_from_codebook_indices(self, quantized_indices):               # soundstream.py:691-699
         assert quantized_indices.dtype in (torch.long, torch.int32)
         if quantized_indices.ndim == 3:
@@ -444,20 +475,26 @@ class SoundStream(nn.Module):
             quantized_indices = quantized_indices.reshape(b, n, self.rq_groups, gq // self.rq_groups).permute(2, 0, 1, 3)   # 'b n (g q) -> g b n q'
         return self.decode(self.rq.get_output_from_indices(quantized_indices))
 
-    @torch.no_grad()
     def decode(self, x, quantize=False):                                      # soundstream.py:701-709
-        """x fp32 (b, n, codebook_dim) -> wave (b, input_channels, n * prod(strides)): 'b n c -> b c n', then the causal transposed-conv decoder."""
-        if quantize:
-            x, *_ = self.rq(x)
-        if not x.is_cuda:
-            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
-        h = ops.bct_to_btc(x.to(F32).contiguous())                           # the same per-batch 2-D transpose, applied to (n, c) -> (c, n)
-        if self.decoder_attn is not None:                                    # :705-706
-            h = self.decoder_attn.run_bct(h)
-        for layer in self.decoder:
-            if isinstance(layer, CausalConv1d):
-                h = layer.run(h)
-            else:
-                for sub in layer:
-                    h = sub(h)
-        return h
+        """x fp32 (b, n, codebook_dim) -> wave (b, input_channels, n * prod(strides)): 'b n c -> b c n', then the causal transposed-conv decoder.
+        A graph is built only in training mode with grad mode on (the decoder's parameters, and x if it requires grad)."""
+        with torch.set_grad_enabled(torch.is_grad_enabled() and self.training):
+            if quantize:
+                x, *_ = self.rq(x)
+            if not x.is_cuda:
+                raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
+            x = x.to(F32).contiguous()
+            grad = codec_bwd.wants_grad(self.decoder, x)
+            if grad and self.decoder_attn is not None:
+                raise NotImplementedError('training-mode SoundStream with use_local_attn=True needs the LocalTransformer backward, which is not '
+                                          'implemented (construct with use_local_attn=False, or call eval())')
+            h = codec_bwd.BctToBtcFn.apply(x) if grad and x.requires_grad else ops.bct_to_btc(x)     # the same per-batch 2-D transpose, (n, c) -> (c, n)
+            if self.decoder_attn is not None:                                # :705-706
+                h = self.decoder_attn.run_bct(h)
+            for layer in self.decoder:
+                if isinstance(layer, CausalConv1d):
+                    h = layer.call(h)
+                else:
+                    for sub in layer:
+                        h = sub(h)
+            return h

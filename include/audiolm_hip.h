@@ -393,6 +393,22 @@ int alm_rvq_pack(const float* E, float* Et, float* e2, int Q, int C, int d, void
 int alm_rvq_encode(const float* x, long long ldx, const float* E, const float* Et, const float* e2, long long* idx, long long ldi, float* quant,
                    long long ldq, int T, int d, int C, int Q, void* stream);
 int alm_bct_to_btc(const float* in, float* out, int B, int C, int T, void* stream);   /* 'b c n -> b n c', soundstream.py:823 */
+/* backward of the codec's conv stacks (csrc/codec_bwd.hip), exact fp32 on the matrix core, no float atomics (bitwise reproducible).  g = dL/dout
+ * [B][Cout][Tout]; y = the saved post-ELU output of the conv (same shape) or NULL: g is read as g * (y > 0 ? 1 : y + 1) (ELU backward fused into
+ * the load).  Shapes, pad and zero_pad as in alm_conv1d_causal.
+ *   alm_conv1d_dgrad : dx [B][Cin][Tin] = the input gradient incl. the reflect fold (+ residual [B][Cin][Tin] if given).  wt = alm_conv1d_pack
+ *                      image of the TRANSPOSED weight [Cin][Cout][k] (alm_conv1d_packed_floats(Cin, Cout, k) floats).
+ *   alm_conv1d_wgrad : dw [Cout][Cin][k], db [Cout] from x [B][Cin][Tin]: one partial per time chunk (alm_conv1d_wgrad_chunk(B, Tout) steps) and
+ *                      32 x 32 channel tile into ws, then summed in chunk order.  ws: alm_conv1d_wgrad_ws_floats floats, owned by the caller.
+ *   alm_phase_deinterleave : adjoint of alm_phase_interleave, g [B][Cout][n * s] -> y [B][s * Cout][n].
+ * The adjoint of alm_bct_to_btc is alm_bct_to_btc with C and T exchanged. */
+int alm_conv1d_wgrad_chunk(int B, int Tout);
+int alm_conv1d_wgrad_ws_floats(int B, int Cin, int Cout, int Tout, int ksize);
+int alm_conv1d_dgrad(const float* g, const float* y, const float* wt, const float* residual, float* dx, int B, int Cin, int Cout, int Tin, int ksize,
+                     int stride, int dilation, int zero_pad, void* stream);
+int alm_conv1d_wgrad(const float* g, const float* y, const float* x, float* dw, float* db, float* ws, long long ws_floats, int B, int Cin, int Cout,
+                     int Tin, int ksize, int stride, int dilation, int zero_pad, void* stream);
+int alm_phase_deinterleave(const float* g, float* y, int B, int Cout, int s, int n, void* stream);
 /* input resampling (soundstream.py:779-795: process_input calls torchaudio.functional.resample(x, input_sample_hz, target_sample_hz); torchaudio's
  * windowed-sinc polyphase resampler, third-party, restated in audiolm-pytorch_amd/resample.py), fp32.  o / n = orig / new rate over their gcd,
  * table [n][taps] = the sinc kernel (taps = 2 W + o, built on the host), rows of len_in samples x [rows][ld_x] -> len_out = ceil(n len_in / o)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd]"""
 import os
 import sys
 import time
@@ -249,6 +249,53 @@ def bench_convs():
     for name, t, tf, gb in rows:
         print(f'{name:40s} {t:7.3f} ms  {tf:6.1f} TF fp32  {gb:7.0f} GB/s')
     print(f'total {tot:.2f} ms')
+
+
+def bench_convs_bwd():
+    """backward kernels of the codec's conv stacks (csrc/codec_bwd.hip) at the config-5 encoder / decoder stage shapes (8 x 30 s @ 24 kHz): input
+    gradient (reflect fold + ELU backward fused), weight + bias gradient (chunk partials + ordered sum), next to the forward launch and to ATen's
+    convolution_backward on the same box (the vendor yardstick, NOT part of the product; it gets the already padded input and no ELU)."""
+    import torch.nn.functional as F
+    torch.manual_seed(0)
+    B, T0 = 8, 720000
+    PEAK = 157.3                                                  # TFLOP/s, v_mfma_f32_32x32x2_f32
+    # (name, Cin, Cout, T, k, stride, dil, zero_pad, elu)
+    shapes = [('enc first', 1, 32, T0, 7, 1, 1, False, False)]
+    for c, t, s in ((32, T0, 2), (64, T0 // 2, 4), (128, T0 // 8, 5), (256, T0 // 40, 8)):
+        shapes += [(f'unit{c} k7 d1', c, c, t, 7, 1, 1, False, True), (f'unit{c} k7 d9', c, c, t, 7, 1, 9, False, True),
+                   (f'unit{c} k1', c, c, t, 1, 1, 1, False, True), (f'enc down s{s}', c, 2 * c, t, 2 * s, s, 1, False, False),
+                   (f'dec up s{s} (k2 form)', 2 * c, s * c, t // s, 2, 1, 1, True, False)]
+    shapes += [('enc last', 512, 512, T0 // 320, 3, 1, 1, False, False), ('dec first', 512, 512, T0 // 320, 7, 1, 1, False, False),
+               ('dec last', 32, 1, T0, 7, 1, 1, False, False)]
+    only = os.environ.get('KBENCH_CONVS_BWD_ATEN', '1') != '0'
+    print(f'{"shape":48s} {"fwd":>8s} {"dgrad":>8s} {"TF":>6s} {"peak":>5s} {"wgrad":>8s} {"TF":>6s} {"peak":>5s} {"aten bwd":>9s} {"ours/aten":>9s}', flush=True)
+    tot = [0.0, 0.0, 0.0, 0.0]
+    for name, cin, cout, t, k, s, d, zp, elu in shapes:
+        x = torch.randn(B, cin, t, device=dev) * 0.5
+        w = torch.randn(cout, cin, k, device=dev) * (cin * k) ** -0.5
+        b = torch.randn(cout, device=dev) * 0.1
+        wp, wt = ops.conv1d_pack(w), ops.conv1d_pack_t(w)
+        fwd = lambda: ops.conv1d_causal(x, wp, b, cout, k, stride=s, dilation=d, elu=elu, zero_pad=zp)      # noqa: E731
+        y = fwd()
+        g = torch.randn_like(y)
+        ys = y if elu else None
+        t_f = timeit(fwd, iters=3, warm=1)
+        t_d = timeit(lambda: ops.conv1d_dgrad(g, ys, wt, cin, t, k, stride=s, dilation=d, zero_pad=zp), iters=3, warm=1)
+        t_w = timeit(lambda: ops.conv1d_wgrad(g, ys, x, k, stride=s, dilation=d, zero_pad=zp), iters=3, warm=1)
+        fl = 2.0 * y.numel() * cin * k / 1e9                      # GFLOP of each of fwd / dgrad / wgrad
+        t_a = float('nan')
+        if only:
+            pad = d * (k - 1) + 1 - s
+            xp = F.pad(x, (pad, 0)) if (zp or pad == 0) else F.pad(x, (pad, 0), mode='reflect')
+            aten = lambda: torch.ops.aten.convolution_backward(g, xp, w, [cout], [s], [0], [d], False, [0], 1, [True, True, True])      # noqa: E731
+            t_a = timeit(aten, iters=3, warm=1)
+            del xp
+        for i, v in enumerate((t_f, t_d, t_w, t_a)):
+            tot[i] += v
+        print(f'{name + f" {cin}->{cout} k{k} s{s} d{d} T={t}":48s} {t_f:8.3f} {t_d:8.3f} {fl / t_d:6.1f} {fl / t_d / PEAK:5.2f} {t_w:8.3f} {fl / t_w:6.1f} '
+              f'{fl / t_w / PEAK:5.2f} {t_a:9.3f} {(t_d + t_w) / t_a:9.2f}', flush=True)
+        del x, y, g, ys
+    print(f'sum over the listed launches (ms): fwd {tot[0]:.2f}  dgrad {tot[1]:.2f}  wgrad {tot[2]:.2f}  aten bwd {tot[3]:.2f}')
 
 
 def bench_e2e():
