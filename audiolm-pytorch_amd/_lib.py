@@ -134,6 +134,12 @@ SIGNATURES = {
     'alm_layernorm_bct': [_P, _P, _P, _P, _I, _I, _I, _F, _P],
     'alm_geglu_bct': [_P, _P, _I, _I, _I, _P],
     'alm_local_attn': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    'alm_local_attn_bwd_supported': [_I, _I],
+    'alm_local_attn_bwd_ws_floats': [_I, _I, _I, _I, _I],
+    'alm_local_attn_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _P],
+    'alm_layernorm_bct_bwd_ws_floats': [_I, _I],
+    'alm_layernorm_bct_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    'alm_geglu_bct_bwd': [_P, _P, _P, _I, _I, _I, _P],
     'alm_conv1d_causal_pre': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'alm_lstm_launches': [_I, _I],
     'alm_lstm_seq': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],

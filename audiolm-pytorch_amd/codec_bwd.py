@@ -1,5 +1,6 @@
-"""Autograd layer of the codec's conv stacks: `torch.autograd.Function`s over the backward kernels of csrc/codec_bwd.hip for CausalConv1d,
-CausalConvTranspose1d and the ResidualUnit (reference soundstream.py:332-369), plus the layout transpose.  soundstream.py takes them ONLY in training
+"""Autograd layer of the codec: `torch.autograd.Function`s over the backward kernels of csrc/codec_bwd.hip for CausalConv1d,
+CausalConvTranspose1d and the ResidualUnit (reference soundstream.py:332-369), plus the layout transpose, and over csrc/local_attn_bwd.hip for the two
+halves of a LocalTransformer layer (LocalMHA, feed-forward; soundstream.py:397-440).  soundstream.py takes them ONLY in training
 mode with grad mode on and an input or parameter that requires grad; every other call issues the forward launches it always did.
 
 The forward of each Function runs the SAME forward kernels as the eval path (the ResidualUnit as its two alm_conv1d_causal launches, to which the
@@ -124,3 +125,83 @@ class BctToBtcFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return ops.bct_to_btc(g.to(F32).contiguous())
+
+
+# ---------------------------------------------------------------------------------------------- LocalTransformer (csrc/local_attn_bwd.hip)
+
+def _lin_bwd(img, lin, g, x, need_x, need_w, residual=None):
+    """(dx | None, dW | None, db | None) of an nn.Linear along the channel axis of [B, C, T] (a k = 1 conv; img: its soundstream._Linear1x1)"""
+    dx = dw = db = None
+    if need_x:
+        dx = ops.conv1d_dgrad(g, None, img.packed_t(lin), x.shape[1], x.shape[2], 1, residual=residual)
+    if need_w:
+        dw, db = ops.conv1d_wgrad(g, None, x, 1)
+        dw = dw.squeeze(-1)
+        if lin.bias is None:
+            db = None
+    return dx, dw, db
+
+
+class LocalMHAFn(torch.autograd.Function):
+    """to_out(local_attn(to_qkv(LN(x)), gates = to_v_gate(LN(x)))) (+ x): the launches of LocalMHA.run.  Saved: x, LN(x), qkv, gates and the gated
+    attention output o (2 dim + 4 H dh + H floats per frame); mean / rstd, the softmax statistics and the pre-gate output are recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, norm_w, norm_b, w_qkv, q_scale, k_scale, w_gate, b_gate, w_out, mod, add_residual):
+        xn, qkv, gates, o, y = mod.launches(x, add_residual)
+        ctx.mod, ctx.add_residual = mod, add_residual
+        ctx.save_for_backward(x, xn, qkv, gates, o, norm_w, w_qkv, q_scale, k_scale, w_gate, w_out)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, xn, qkv, gates, o, norm_w, _, q_scale, k_scale, _, _ = ctx.saved_tensors
+        mod, need = ctx.mod, ctx.needs_input_grad
+        l_qkv, l_gate, l_out = mod._lin
+        g = g.to(F32).contiguous()
+        do, dw_out, _ = _lin_bwd(l_out, mod.to_out, g, o, True, need[8])
+        cos_t, sin_t, xpos_t = mod.tables(x.device)
+        dqkv, dgates, dqs, dks = ops.local_attn_bwd(qkv, q_scale.detach().to(F32), k_scale.detach().to(F32), cos_t, sin_t, xpos_t, gates, o, do, mod.heads,
+                                                    mod.dim_head, mod.window_size, mod.qk_scale)
+        need_ln = need[0] or need[1] or need[2]
+        dxn, dw_qkv, _ = _lin_bwd(l_qkv, mod.to_qkv, dqkv, xn, need_ln, need[3])
+        dxn, dw_gate, db_gate = _lin_bwd(l_gate, mod.to_v_gate[0], dgates, xn, need_ln, need[6] or need[7], residual=dxn)      # dxn = both branches' sum
+        dx = dgamma = dbeta = None
+        if need_ln:
+            dx, dgamma, dbeta = ops.layernorm_bct_bwd(dxn, x, norm_w.detach().to(F32), mod.norm.eps, residual=g if ctx.add_residual else None,
+                                                      need_params=need[1] or need[2])
+        return (dx if need[0] else None, dgamma, dbeta, dw_qkv, dqs if need[4] else None, dks if need[5] else None, dw_gate, db_gate, dw_out, None, None)
+
+
+class LocalFeedForwardFn(torch.autograd.Function):
+    """W2(GEGLU(W1(LN(x)))) + x: the launches of LocalTransformer's feed-forward half.  Saved: x, LN(x), the pre-activation u = W1 LN(x) and
+    h = GEGLU(u) (2 dim + 3 I floats per frame)."""
+
+    @staticmethod
+    def forward(ctx, x, norm_w, norm_b, w1, w2, ff, lins):
+        xn, u, h, y = ff_launches(ff, lins, x)
+        ctx.ff, ctx.lins = ff, lins
+        ctx.save_for_backward(x, xn, u, h, norm_w, w1, w2)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, xn, u, h, norm_w, _, _ = ctx.saved_tensors
+        ff, lins, need = ctx.ff, ctx.lins, ctx.needs_input_grad
+        g = g.to(F32).contiguous()
+        dh, dw2, _ = _lin_bwd(lins[1], ff[4], g, h, True, need[4])
+        du = ops.geglu_bct_bwd(dh, u)
+        need_ln = need[0] or need[1] or need[2]
+        dxn, dw1, _ = _lin_bwd(lins[0], ff[1], du, xn, need_ln, need[3])
+        dx = dgamma = dbeta = None
+        if need_ln:
+            dx, dgamma, dbeta = ops.layernorm_bct_bwd(dxn, x, norm_w.detach().to(F32), ff[0].eps, residual=g, need_params=need[1] or need[2])
+        return dx if need[0] else None, dgamma, dbeta, dw1, dw2, None, None
+
+
+def ff_launches(ff, lins, x):
+    """(LN(x), u, GEGLU(u), W2 GEGLU(u) + x) of one feed-forward block (ff: the Sequential, lins: its two soundstream._Linear1x1)"""
+    xn = ops.layernorm_bct(x, ff[0].weight.detach(), ff[0].bias.detach(), ff[0].eps)
+    u = lins[0](ff[1], xn)
+    h = ops.geglu_bct(u)
+    return xn, u, h, lins[1](ff[4], h, residual=x)

@@ -1177,6 +1177,73 @@ def local_attn(qkv, q_scale, k_scale, cos_t, sin_t, xpos_t, gates, heads, dim_he
     return out
 
 
+# ---- their backward (csrc/local_attn_bwd.hip), exact fp32, no atomics
+
+def local_attn_bwd_supported(dim_head, window):
+    """the geometries alm_local_attn_bwd covers, which are those of alm_local_attn: dim_head in {32, 64}, window <= 256, 4 dim_head window floats of LDS <= 160 KiB"""
+    return bool(_lib.query('alm_local_attn_bwd_supported', int(dim_head), int(window)))
+
+
+def local_attn_bwd(qkv, q_scale, k_scale, cos_t, sin_t, xpos_t, gates, o, do, heads, dim_head, window, scale):
+    """qkv / gates / slot tables as for local_attn, o = its saved (gated) output, do = dL/do [B, H dh, T] ->
+    (dqkv [B, 3 H dh, T], dgates [B, H, T], dq_scale [dh], dk_scale [dh])"""
+    for t in (qkv, gates, o, do):
+        _chk(t, F32)
+    B, C3, T = qkv.shape
+    assert qkv.is_contiguous() and C3 == 3 * heads * dim_head
+    assert gates.is_contiguous() and tuple(gates.shape) == (B, heads, T)
+    assert o.is_contiguous() and do.is_contiguous() and tuple(o.shape) == tuple(do.shape) == (B, heads * dim_head, T)
+    for t in (cos_t, sin_t, xpos_t):
+        assert t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == (2 * window, dim_head) and t.device == qkv.device
+    for t in (q_scale, k_scale):
+        assert t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == (dim_head,) and t.device == qkv.device
+    if not local_attn_bwd_supported(dim_head, window):
+        raise _lib.AlmError(f'local_attn_bwd: dim_head {dim_head} / window {window} is outside the kernel\'s envelope (dim_head 32 or 64, window <= 256, '
+                            'dim_head 64 up to window 160)')
+    n = _lib.query('alm_local_attn_bwd_ws_floats', B, heads, dim_head, T, window)
+    if n < 0:
+        raise _lib.AlmError('local_attn_bwd: the workspace exceeds 2^31 floats')
+    ws = _new((n,), dtype=F32, device=qkv.device)
+    dqkv = _new_like(qkv)
+    dgates = _new_like(gates)
+    dqs = _new((dim_head,), dtype=F32, device=qkv.device)
+    dks = _new((dim_head,), dtype=F32, device=qkv.device)
+    _lib.call('alm_local_attn_bwd', qkv.data_ptr(), q_scale.data_ptr(), k_scale.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(), xpos_t.data_ptr(),
+              gates.data_ptr(), o.data_ptr(), do.data_ptr(), dqkv.data_ptr(), dgates.data_ptr(), dqs.data_ptr(), dks.data_ptr(), ws.data_ptr(), n,
+              B, heads, dim_head, T, window, float(scale), _st())
+    return dqkv, dgates, dqs, dks
+
+
+def layernorm_bct_bwd(dy, x, gamma, eps=1e-5, *, residual=None, need_params=True):
+    """dy, x (the forward input) fp32 [B, C, T], gamma [C] -> (dx [B, C, T] (+ residual), dgamma [C] | None, dbeta [C] | None)"""
+    _chk(dy, F32), _chk(x, F32), _chk(gamma, F32)
+    B, C, T = x.shape
+    assert x.is_contiguous() and dy.is_contiguous() and dy.shape == x.shape and gamma.is_contiguous() and tuple(gamma.shape) == (C,)
+    if residual is not None:
+        _chk(residual, F32)
+        assert residual.shape == x.shape and residual.is_contiguous()
+    n = _lib.query('alm_layernorm_bct_bwd_ws_floats', B, T)
+    if n < 0:
+        raise _lib.AlmError('layernorm_bct_bwd: the statistics workspace exceeds 2^31 floats')
+    ws = _new((n,), dtype=F32, device=x.device)
+    dx = _new_like(x)
+    dgamma = _new((C,), dtype=F32, device=x.device) if need_params else None
+    dbeta = _new((C,), dtype=F32, device=x.device) if need_params else None
+    _lib.call('alm_layernorm_bct_bwd', dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), _p(residual), dx.data_ptr(), _p(dgamma), _p(dbeta), ws.data_ptr(),
+              B, C, T, float(eps), _st())
+    return dx, dgamma, dbeta
+
+
+def geglu_bct_bwd(dh, u):
+    """dh fp32 [B, I, T], u fp32 [B, 2 I, T] (the input of geglu_bct) -> du [B, 2 I, T]"""
+    _chk(dh, F32), _chk(u, F32)
+    B, C2, T = u.shape
+    assert u.is_contiguous() and dh.is_contiguous() and C2 % 2 == 0 and tuple(dh.shape) == (B, C2 // 2, T)
+    du = _new_like(u)
+    _lib.call('alm_geglu_bct_bwd', dh.data_ptr(), u.data_ptr(), du.data_ptr(), B, C2 // 2, T, _st())
+    return du
+
+
 # ---- HuBERT feature model (csrc/hubert.hip; conv1d_valid and mha_attn are the shared fp32 kernels of csrc/dense_f32.hip) ----
 def hubert_conv0_stats(wave, w, stride, eps=1e-5):
     """wave fp32 [B, Tin] (unit element stride), w fp32 [C, k] -> stats fp32 [B, C, 2] = (mean, rstd) over time of conv1d(wave, w, stride), the

@@ -5,7 +5,8 @@ return_codes_only=True)` -- the causal-conv encoder (soundstream.py:332-380, 519
 decoder :347-360, 382-395, 615-627) run on the MI355X kernels of csrc/codec.hip (exact-fp32 MFMA).  Everything else the reference class
 does (discriminators, losses, train-mode RVQ, LFQ / FSQ quantizers) is out of scope and raises.  The conv encoder / decoder are
 differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
-build a graph over the backward kernels of csrc/codec_bwd.hip (codec_bwd.py; use_local_attn=True raises there: no LocalTransformer backward).
+build a graph over the backward kernels of csrc/codec_bwd.hip and, for the LocalTransformer of use_local_attn=True, csrc/local_attn_bwd.hip (codec_bwd.py;
+attn_dim_head outside {32, 64} or a window outside the attention kernels' envelope raises there).
 `encoder_attn` / `decoder_attn` (soundstream.py:397-440, 545, 613): local-attention's LocalMHA + FeedForward (third-party source, not vendored:
 restated, parity unpinned -- oracle/local_attention_restated.py) run in the codec's [B, C, T] layout: LayerNorm / windowed causal attention with
 qk-l2norm, rotary + xpos and per-head value gates / GEGLU are csrc/local_attn.hip, the Linear layers are k = 1 convs on the exact-fp32 MFMA kernel.
@@ -241,11 +242,25 @@ class GroupedResidualVQ(nn.Module):
 
 # ---------------------------------------------------------------------------------------------- LocalTransformer (soundstream.py:397-440)
 
+_NO_ATTN_BWD = ('training-mode LocalTransformer backward exists for attn_dim_head 32 and 64 with attn_window_size <= 256 (dim_head 64: <= 160) only; got '
+                'dim_head {} / window {} (call eval(), or construct the SoundStream with use_local_attn=False)')
+
+
+def _btc(x, grad):
+    """'b c n -> b n c' (or back); grad: the caller builds a graph (codec_bwd.wants_grad)"""
+    return codec_bwd.BctToBtcFn.apply(x) if grad and x.requires_grad else ops.bct_to_btc(x)
+
+
 class _Linear1x1:
     """an nn.Linear applied along the channel axis of [B, C, T] = a k = 1 conv on the exact-fp32 MFMA kernel; packed weight cached per version"""
 
     def __init__(self):
         self._packed = None
+        self._packed_t = codec_bwd._ImageCache()                  # transposed image for the input gradient (training mode only)
+
+    def packed_t(self, lin):
+        w = lin.weight
+        return self._packed_t.get((w,), lambda: ops.conv1d_pack_t(w.detach().to(F32).unsqueeze(-1).contiguous()))
 
     def __call__(self, lin, x, residual=None):
         w, b = lin.weight, lin.bias
@@ -299,23 +314,43 @@ class LocalMHA(nn.Module):
         self._lin = [_Linear1x1() for _ in range(3)]
         self._tables = None
 
-    def run(self, x, add_residual=True):
-        """x fp32 [B, dim, T] -> attn(x) (+ x), same layout"""
+    def tables(self, device):
         inv = self.attn_fn.rel_pos.inv_freq
-        key = (inv.data_ptr(), core.tensor_version(inv), x.device)
+        key = (inv.data_ptr(), core.tensor_version(inv), device)
         if self._tables is None or self._tables[0] != key:
-            self._tables = (key, self.attn_fn.rel_pos.tables(2 * self.window_size, x.device))
-        cos_t, sin_t, xpos_t = self._tables[1]
+            self._tables = (key, self.attn_fn.rel_pos.tables(2 * self.window_size, device))
+        return self._tables[1]
+
+    def launches(self, x, add_residual=True):
+        """(LN(x), qkv, gates, gated attention output, attn(x) (+ x)): the forward launches, shared by the eval path and the autograd Function"""
+        cos_t, sin_t, xpos_t = self.tables(x.device)
         xn = ops.layernorm_bct(x, self.norm.weight.detach(), self.norm.bias.detach(), self.norm.eps)
         qkv = self._lin[0](self.to_qkv, xn)
         gates = self._lin[1](self.to_v_gate[0], xn)                      # from the NORMED input (LocalMHA.forward re-binds x)
         o = ops.local_attn(qkv, self.q_scale.detach(), self.k_scale.detach(), cos_t, sin_t, xpos_t, gates, self.heads, self.dim_head,
                            self.window_size, self.qk_scale)
-        return self._lin[2](self.to_out, o, residual=x if add_residual else None)
+        return xn, qkv, gates, o, self._lin[2](self.to_out, o, residual=x if add_residual else None)
+
+    def backward_supported(self):
+        return ops.local_attn_bwd_supported(self.dim_head, self.window_size)
+
+    def run(self, x, add_residual=True):
+        """x fp32 [B, dim, T] -> attn(x) (+ x), same layout"""
+        return self.launches(x, add_residual)[-1]
+
+    def call(self, x, add_residual=True):
+        """run(), or its autograd Function in training mode with grad mode on and something that requires grad"""
+        if codec_bwd.wants_grad(self, x):
+            if not self.backward_supported():
+                raise NotImplementedError(_NO_ATTN_BWD.format(self.dim_head, self.window_size))
+            return codec_bwd.LocalMHAFn.apply(x, self.norm.weight, self.norm.bias, self.to_qkv.weight, self.q_scale, self.k_scale,
+                                              self.to_v_gate[0].weight, self.to_v_gate[0].bias, self.to_out.weight, self, add_residual)
+        return self.run(x, add_residual)
 
     def forward(self, x):
         """reference layout: x (b, n, dim) -> attention output WITHOUT the residual (the caller adds it, soundstream.py:437)"""
-        return ops.bct_to_btc(self.run(ops.bct_to_btc(x.to(F32).contiguous()), add_residual=False))      # (n, c) -> (c, n) and back
+        grad = codec_bwd.wants_grad(self, x)
+        return _btc(self.call(_btc(x.to(F32).contiguous(), grad), add_residual=False), grad)             # (n, c) -> (c, n) and back
 
 
 class _GEGLU(nn.Module):
@@ -340,21 +375,33 @@ class LocalTransformer(nn.Module):
                                      for _ in range(depth)])
         self._ff_lin = [[_Linear1x1(), _Linear1x1()] for _ in range(depth)]
 
+    def backward_supported(self):
+        return all(attn.backward_supported() for attn, _ in self.layers)
+
+    def check_backward(self, *tensors):
+        """raises, before any launch, when a graph would be built (codec_bwd.wants_grad) for a geometry that has no backward kernel"""
+        if codec_bwd.wants_grad(self, *tensors) and not self.backward_supported():
+            attn = self.layers[0][0]
+            raise NotImplementedError(_NO_ATTN_BWD.format(attn.dim_head, attn.window_size))
+
     def run_bct(self, x):
-        """x fp32 [B, dim, T] (codec layout) -> same: x = attn(x) + x; x = ff(x) + x per layer (soundstream.py:436-438)"""
+        """x fp32 [B, dim, T] (codec layout) -> same: x = attn(x) + x; x = ff(x) + x per layer (soundstream.py:436-438).  In training mode with grad
+        mode on and an input or parameter that requires grad, each half is one autograd Function over the same launches (codec_bwd.py)."""
+        self.check_backward(x)
         for (attn, ff), lins in zip(self.layers, self._ff_lin):
-            x = attn.run(x)
-            h = ops.layernorm_bct(x, ff[0].weight.detach(), ff[0].bias.detach(), ff[0].eps)
-            h = ops.geglu_bct(lins[0](ff[1], h))
-            x = lins[1](ff[4], h, residual=x)
+            x = attn.call(x)
+            if codec_bwd.wants_grad(ff, x):
+                x = codec_bwd.LocalFeedForwardFn.apply(x, ff[0].weight, ff[0].bias, ff[1].weight, ff[4].weight, ff, lins)
+            else:
+                x = codec_bwd.ff_launches(ff, lins, x)[-1]
         return x
 
-    @torch.no_grad()
     def forward(self, x):
         """x (b, n, dim) -> (b, n, dim)"""
         if not x.is_cuda:
             raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
-        return ops.bct_to_btc(self.run_bct(ops.bct_to_btc(x.to(F32).contiguous())))
+        grad = codec_bwd.wants_grad(self, x)
+        return _btc(self.run_bct(_btc(x.to(F32).contiguous(), grad)), grad)
 
 
 def curtail_to_multiple(t, mult, from_left=False):               # soundstream.py:86-90
@@ -427,10 +474,8 @@ class SoundStream(nn.Module):
         if not x.is_cuda:
             raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
         h = x.to(F32).contiguous()
-        grad = codec_bwd.wants_grad(self.encoder, h)
-        if grad and self.encoder_attn is not None:
-            raise NotImplementedError('training-mode SoundStream with use_local_attn=True needs the LocalTransformer backward, which is not implemented '
-                                      '(construct with use_local_attn=False, or call eval())')
+        if self.encoder_attn is not None:                        # a geometry without a backward kernel raises before any launch
+            self.encoder_attn.check_backward(h, *self.encoder.parameters())
         for layer in self.encoder:
             if isinstance(layer, CausalConv1d):
                 h = layer.call(h)
@@ -485,9 +530,9 @@ class SoundStream(nn.Module):
                 raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
             x = x.to(F32).contiguous()
             grad = codec_bwd.wants_grad(self.decoder, x)
-            if grad and self.decoder_attn is not None:
-                raise NotImplementedError('training-mode SoundStream with use_local_attn=True needs the LocalTransformer backward, which is not '
-                                          'implemented (construct with use_local_attn=False, or call eval())')
+            if self.decoder_attn is not None:                                # a geometry without a backward kernel raises before any launch
+                self.decoder_attn.check_backward(x)
+                grad = grad or codec_bwd.wants_grad(self.decoder_attn, x)
             h = codec_bwd.BctToBtcFn.apply(x) if grad and x.requires_grad else ops.bct_to_btc(x)     # the same per-batch 2-D transpose, (n, c) -> (c, n)
             if self.decoder_attn is not None:                                # :705-706
                 h = self.decoder_attn.run_bct(h)

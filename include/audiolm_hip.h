@@ -478,6 +478,27 @@ int alm_layernorm_bct(const float* x, const float* gamma, const float* beta, flo
 int alm_geglu_bct(const float* x, float* out, int B, int I, int T, void* stream);
 int alm_local_attn(const float* qkv, const float* q_scale, const float* k_scale, const float* cos_t, const float* sin_t, const float* xpos_t,
                    const float* gates, float* out, int B, int H, int dim_head, int T, int window, float scale, void* stream);
+/* backward of the three (csrc/local_attn_bwd.hip), exact fp32, no atomics: every sum has a fixed order (bitwise reproducible).
+ *   alm_local_attn_bwd : from qkv, the scales, the slot tables, gates (required), o = the saved GATED output of alm_local_attn and dO = dL/do:
+ *                       dqkv [B][3 H dh][T], dgates [B][H][T] (pre-sigmoid), dq_scale / dk_scale [dh].  Three launches: the dQ pass (one thread per
+ *                       query; also dgates, and lse / delta into ws), the dK/dV pass (one thread per key over the queries j .. j + window that see
+ *                       it) and the finish of the scale gradients, which adds one partial per (b, h, window) in that order.
+ *                       ws: alm_local_attn_bwd_ws_floats = 2 B H T + 2 B H ceil(T / window) dh floats, owned by the caller (-1: past 2^31).
+ *                       alm_local_attn_bwd_supported(dh, window) = 1 iff dh in {32, 64}, window <= 256 and 4 dh window floats of LDS fit 160 KiB
+ *                       (dh 64: window <= 160) -- exactly what alm_local_attn accepts; anything else is ALM_ERR_UNSUPPORTED.
+ *   alm_layernorm_bct_bwd : dx [B][C][T] (+ residual [B][C][T] if given) from dy and the forward INPUT x (mean / rstd are recomputed, and kept in
+ *                       ws [2][B][T] = alm_layernorm_bct_bwd_ws_floats floats for the second launch); dgamma / dbeta [C] (both or neither) as one
+ *                       workgroup per channel, thread-strided sums and a fixed tree.
+ *   alm_geglu_bct_bwd : du [B][2 I][T] from dh [B][I][T] and the saved pre-activation u [B][2 I][T] (erf GELU and its exact derivative). */
+int alm_local_attn_bwd_supported(int dim_head, int window);
+int alm_local_attn_bwd_ws_floats(int B, int H, int dim_head, int T, int window);
+int alm_local_attn_bwd(const float* qkv, const float* q_scale, const float* k_scale, const float* cos_t, const float* sin_t, const float* xpos_t,
+                       const float* gates, const float* o, const float* dO, float* dqkv, float* dgates, float* dq_scale, float* dk_scale, float* ws,
+                       long long ws_floats, int B, int H, int dim_head, int T, int window, float scale, void* stream);
+int alm_layernorm_bct_bwd_ws_floats(int B, int T);
+int alm_layernorm_bct_bwd(const float* dy, const float* x, const float* gamma, const float* residual, float* dx, float* dgamma, float* dbeta,
+                          float* ws, int B, int C, int T, float eps, void* stream);
+int alm_geglu_bct_bwd(const float* dh, const float* u, float* du, int B, int I, int T, void* stream);
 
 /* ---- EnCodec 24 kHz (csrc/encodec.hip): the causal SEANet encoder / decoder and LSTM that the reference's encodec.py:25-177 runs through Meta's model,
  * restated in tests/encodec_restated.py.  fp32.  The residual VQ is alm_rvq_pack / alm_rvq_encode / alm_rvq_decode above.

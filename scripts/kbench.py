@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd]"""
 import os
 import sys
 import time
@@ -296,6 +296,62 @@ def bench_convs_bwd():
               f'{fl / t_w / PEAK:5.2f} {t_a:9.3f} {(t_d + t_w) / t_a:9.2f}', flush=True)
         del x, y, g, ys
     print(f'sum over the listed launches (ms): fwd {tot[0]:.2f}  dgrad {tot[1]:.2f}  wgrad {tot[2]:.2f}  aten bwd {tot[3]:.2f}')
+
+
+def bench_local_attn_bwd():
+    """LocalTransformer backward (csrc/local_attn_bwd.hip) at the default geometry, B = 8, dim 512, 8 heads x 64, window 128, T = 2250 frames (30 s at
+    24 kHz / 320): the attention backward (dQ pass + dK/dV pass + scale finish, one call), LayerNorm backward and GEGLU backward next to their forward
+    launches, the whole block forward and forward + backward, and decode(encode(x)) forward + backward with use_local_attn=True against False."""
+    import torch.nn.functional as F
+    from audiolm_pytorch_amd import soundstream as S
+    torch.manual_seed(0)
+    B, T, dim, H, dh, W = 8, 2250, 512, 8, 64, 128
+    I = int(dim * 4 * 2 / 3)
+    qkv, gates, do = torch.randn(B, 3 * H * dh, T, device=dev), torch.randn(B, H, T, device=dev), torch.randn(B, H * dh, T, device=dev)
+    qs, ks = torch.ones(dh, device=dev), torch.ones(dh, device=dev)
+    tabs = S._SinusoidalEmbeddings(dh, scale_base=W // 2).tables(2 * W, dev)
+    fwd = lambda: ops.local_attn(qkv, qs, ks, *tabs, gates, H, dh, W, 8)      # noqa: E731
+    o = fwd()
+    t_f = timeit(fwd, iters=20, warm=3)
+    t_b = timeit(lambda: ops.local_attn_bwd(qkv, qs, ks, *tabs, gates, o, do, H, dh, W, 8), iters=20, warm=3)
+    nw = -(-T // W)
+    # GFLOP of one dh-long pass over the visible (query, key) pairs; the forward makes 2 (q . k, p v), the backward 8 (dQ: q . k twice, dO . v, dS k;
+    # dK/dV: q . k, dO . v, p dO, dS q)
+    fl = 2.0 * B * H * dh * sum(min(i, W) + 1 for i in range(T)) / 1e9
+    print(f'local_attn     fwd {t_f:7.3f} ms ({2 * fl / t_f:5.1f} TF fp32 VALU)   bwd (3 launches, {B * H * nw} workgroups x {W}) {t_b:7.3f} ms ({8 * fl / t_b:5.1f} TF)')
+    x, dy = torch.randn(B, dim, T, device=dev), torch.randn(B, dim, T, device=dev)
+    gamma, beta = torch.ones(dim, device=dev), torch.zeros(dim, device=dev)
+    t_f = timeit(lambda: ops.layernorm_bct(x, gamma, beta), iters=20, warm=3)
+    t_b = timeit(lambda: ops.layernorm_bct_bwd(dy, x, gamma, residual=dy), iters=20, warm=3)
+    gb = x.numel() * 4 / 1e6
+    print(f'layernorm_bct  fwd {t_f:7.3f} ms ({2 * gb / t_f:5.0f} GB/s)   bwd (dx + residual, dgamma / dbeta) {t_b:7.3f} ms ({5 * gb / t_b:5.0f} GB/s min. traffic)')
+    u, dhh = torch.randn(B, 2 * I, T, device=dev), torch.randn(B, I, T, device=dev)
+    t_f = timeit(lambda: ops.geglu_bct(u), iters=20, warm=3)
+    t_b = timeit(lambda: ops.geglu_bct_bwd(dhh, u), iters=20, warm=3)
+    gb = dhh.numel() * 4 / 1e6
+    print(f'geglu_bct      fwd {t_f:7.3f} ms ({3 * gb / t_f:5.0f} GB/s)   bwd {t_b:7.3f} ms ({5 * gb / t_b:5.0f} GB/s)')
+    lt = S.LocalTransformer(dim=dim, depth=1, heads=H, window_size=W, dim_head=dh).to(dev)
+    xb = torch.randn(B, dim, T, device=dev)
+    lt.eval()
+    t_f = timeit(lambda: lt.run_bct(xb), iters=10, warm=2)
+    lt.train()
+
+    def step():
+        lt.zero_grad(set_to_none=True)
+        xg = xb.detach().requires_grad_()
+        lt.run_bct(xg).backward(dy)
+    t_fb = timeit(step, iters=10, warm=2)
+    print(f'LocalTransformer block (depth 1) [B={B}, {dim}, T={T}]: forward {t_f:.3f} ms, forward + backward {t_fb:.3f} ms')
+    wave = torch.randn(B, 1, T * 320, device=dev) * 0.1
+    for local in (False, True):
+        ss = A.SoundStream(codebook_size=4096, rq_num_quantizers=8, target_sample_hz=24000, strides=(2, 4, 5, 8), use_local_attn=local).to(dev).train()
+
+        def cstep():
+            ss.zero_grad(set_to_none=True)
+            F.mse_loss(ss.decode(ss.encode(wave)), wave).backward()
+        t = timeit(cstep, iters=3, warm=1)
+        print(f'decode(encode(x)) forward + backward, 8 x 30 s @ 24 kHz, use_local_attn={local}: {t:.1f} ms')
+        del ss
 
 
 def bench_e2e():
