@@ -114,6 +114,15 @@ SIGNATURES = {
     'alm_rvq_pack': [_P, _P, _P, _I, _I, _I, _P],
     'alm_rvq_encode': [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P],
     'alm_bct_to_btc': [_P, _P, _I, _I, _I, _P],
+    'alm_rvq_code_stats_chunk': [],
+    'alm_rvq_code_stats_ws_floats': [_I, _I, _I],
+    'alm_rvq_code_stats': [_P, _L, _P, _L, _P, _P, _P, _L, _I, _I, _I, _P],
+    'alm_rvq_train_quantize_blocks': [_I],
+    'alm_rvq_train_quantize': [_P, _L, _P, _L, _P, _P, _L, _P, _P, _F, _I, _I, _I, _I, _P],
+    'alm_rvq_ema_update': [_P, _P, _P, _P, _P, _F, _F, _F, _P, _P, _I, _I, _P],
+    'alm_rvq_expire': [_P, _I, _P, _P, _L, _P, _L, _P, _I, _I, _F, _P, _P, _P, _I, _I, _I, _P],
+    'alm_rvq_kmeans_update': [_P, _P, _P, _P, _P, _P, _I, _I, _P],
+    'alm_rvq_train_bwd': [_P, _L, _P, _L, _P, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     'alm_conv1d_wgrad_chunk': [_I, _I],
     'alm_conv1d_wgrad_ws_floats': [_I, _I, _I, _I, _I],
     'alm_conv1d_dgrad': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -127,6 +127,33 @@ class BctToBtcFn(torch.autograd.Function):
         return ops.bct_to_btc(g.to(F32).contiguous())
 
 
+class RvqTrainFn(torch.autograd.Function):
+    """one training step of the grouped residual VQ (soundstream.GroupedResidualVQ.train_step): x [M, dim] -> (out, losses [g, Q]; indices carry no
+    gradient).  Saved: x, the indices [g, M, Q] and per group the step's PRE-update codebooks [Q, C, d]; every row's residual chain is recomputed in
+    the backward (alm_rvq_train_bwd) instead of keeping Q residuals.  The codebooks get no gradient (EMA-trained)."""
+
+    @staticmethod
+    def forward(ctx, x, mod, k):
+        out, losses, idx, snaps = mod.train_step(x, k)
+        ctx.cfg = (mod.commitment_weight, mod.rotation_trick)
+        ctx.save_for_backward(x, idx, *snaps)
+        ctx.mark_non_differentiable(idx)
+        return out, losses, idx
+
+    @staticmethod
+    def backward(ctx, g_out, g_losses, _):
+        x, idx, *snaps = ctx.saved_tensors
+        weight, rotation = ctx.cfg
+        M, dim = x.shape
+        dg = dim // len(snaps)
+        g_out = g_out.to(F32).contiguous()
+        dx = torch.empty_like(x)
+        for gi, E in enumerate(snaps):
+            coef = (g_losses[gi].to(F32) * (2. * weight / (M * dg))).contiguous()          # d loss_q / d r = 2 w (r - quant) / (M d)
+            ops.rvq_train_bwd(x[:, gi * dg:(gi + 1) * dg], idx[gi], E, g_out[:, gi * dg:(gi + 1) * dg], coef, dx[:, gi * dg:(gi + 1) * dg], rotation)
+        return dx, None, None
+
+
 # ---------------------------------------------------------------------------------------------- LocalTransformer (csrc/local_attn_bwd.hip)
 
 def _lin_bwd(img, lin, g, x, need_x, need_w, residual=None):

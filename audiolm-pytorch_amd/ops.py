@@ -1046,6 +1046,93 @@ def rvq_encode(x, E, Et, e2, idx_out=None, quant_out=None):
     return idx_out
 
 
+# ---- train-mode residual VQ (csrc/rvq_train.hip): fp32, no atomics, bitwise reproducible
+
+def _idx_col(idx):
+    """(pointer, row stride) of an int64 index column [M] (any stride) or of the first column of an [M, Q] array"""
+    _chk(idx, torch.int64)
+    assert idx.ndim == 1 or idx.stride(1) == 1
+    return idx.data_ptr(), idx.stride(0)
+
+
+def rvq_code_stats_chunk():
+    """rows per chunk of a code's row list in alm_rvq_code_stats (a code with more rows is summed as several partials, added in chunk order)"""
+    return _lib.query('alm_rvq_code_stats_chunk')
+
+
+def rvq_code_stats(r, idx, C, n_out=None, s_out=None):
+    """r fp32 [M, d] (row stride arbitrary), idx int64 [M] (any stride; -1 = skip) -> (n [C] rows per code as floats, s [C, d] their sums)"""
+    _chk(r, F32)
+    M, d = r.shape
+    assert r.stride(1) == 1 and idx.shape == (M,)
+    nws = _lib.query('alm_rvq_code_stats_ws_floats', M, d, C)
+    if nws < 0:
+        raise _lib.AlmError(f'alm_rvq_code_stats: workspace for M = {M}, d = {d}, C = {C} does not fit an int')
+    ws = _new((max(nws, 1),), dtype=F32, device=r.device)
+    n = _new((C,), dtype=F32, device=r.device) if n_out is None else n_out
+    s = _new((C, d), dtype=F32, device=r.device) if s_out is None else s_out
+    assert n.is_contiguous() and s.is_contiguous() and n.shape == (C,) and s.shape == (C, d)
+    ip, ldi = _idx_col(idx)
+    _lib.call('alm_rvq_code_stats', r.data_ptr(), r.stride(0), ip, ldi, n.data_ptr(), s.data_ptr(), ws.data_ptr(), nws, M, d, C, _st())
+    return n, s
+
+
+def rvq_train_quantize(resid, idx, E, out, loss, loss_scale, rotation):
+    """one layer in place: resid [M, d] -= y, out [M, d] view += y, loss (one float) = loss_scale * sum |E[idx] - resid|^2  (alm_rvq_train_quantize)"""
+    _chk(resid, F32), _chk(E, F32), _chk(out, F32), _chk(loss, F32)
+    M, d = resid.shape
+    C = E.shape[0]
+    assert resid.stride(1) == 1 and out.stride(1) == 1 and out.shape == (M, d) and E.is_contiguous() and E.shape == (C, d) and idx.shape == (M,)
+    part = _new((max(_lib.query('alm_rvq_train_quantize_blocks', M), 1),), dtype=F32, device=resid.device)
+    ip, ldi = _idx_col(idx)
+    _lib.call('alm_rvq_train_quantize', resid.data_ptr(), resid.stride(0), ip, ldi, E.data_ptr(), out.data_ptr(), out.stride(0), loss.data_ptr(), part.data_ptr(),
+              float(loss_scale), int(rotation), M, d, C, _st())
+
+
+def rvq_ema_update(cluster_size, embed_avg, embed, n, s, decay, eps, threshold, dead):
+    """EMA + Laplace smoothing + embed rewrite of one layer; dead int32 [1 + C] <- (number of codes below `threshold`, then those codes ascending)"""
+    for t in (cluster_size, embed_avg, embed, n, s):
+        _chk(t, F32)
+        assert t.is_contiguous()
+    C, d = embed.shape[-2:]
+    assert cluster_size.numel() == C and embed_avg.numel() == C * d and n.numel() == C and s.numel() == C * d
+    assert dead.dtype == torch.int32 and dead.is_contiguous() and dead.numel() >= 1 + C
+    total = _new((1,), dtype=F32, device=embed.device)
+    _lib.call('alm_rvq_ema_update', cluster_size.data_ptr(), embed_avg.data_ptr(), embed.data_ptr(), n.data_ptr(), s.data_ptr(), float(decay), float(eps),
+              float(threshold), dead.data_ptr(), total.data_ptr(), C, d, _st())
+
+
+def rvq_expire(dead_codes, count, rows, x, idx, E, q, rotation, threshold, cluster_size, embed_avg, embed):
+    """codes dead_codes[:count] (int32, device) <- the layer-q residual of the rows `rows` (int64 [count], device) of x, recomputed from idx [M, Q] and E [Q, C, d]"""
+    _chk(x, F32), _chk(E, F32), _chk(rows, torch.int64)
+    M, d = x.shape
+    C = E.shape[1]
+    assert x.stride(1) == 1 and E.is_contiguous() and rows.is_contiguous() and rows.numel() == count and idx.stride(1) == 1 and idx.shape[0] == M
+    assert dead_codes.dtype == torch.int32 and dead_codes.is_contiguous() and dead_codes.numel() >= count
+    _lib.call('alm_rvq_expire', dead_codes.data_ptr(), count, rows.data_ptr(), x.data_ptr(), x.stride(0), idx.data_ptr(), idx.stride(0), E.data_ptr(), q,
+              int(rotation), float(threshold), cluster_size.data_ptr(), embed_avg.data_ptr(), embed.data_ptr(), M, d, C, _st())
+
+
+def rvq_kmeans_update(means, n, s, embed=None, embed_avg=None, cluster_size=None):
+    """means [C, d] = n == 0 ? means : s / max(n, 1) in place; with `embed` also embed = means, embed_avg = means * n, cluster_size = n"""
+    _chk(means, F32)
+    C, d = means.shape
+    assert means.is_contiguous() and n.is_contiguous() and s.is_contiguous()
+    _lib.call('alm_rvq_kmeans_update', means.data_ptr(), n.data_ptr(), s.data_ptr(), _p(embed), _p(embed_avg), _p(cluster_size), C, d, _st())
+
+
+def rvq_train_bwd(x, idx, E, g_out, coef, dx, rotation):
+    """dx [M, d] view <- the input gradient of the train-mode residual VQ of one group (alm_rvq_train_bwd); g_out [M, d] view or None, coef [Q] or None"""
+    _chk(x, F32), _chk(E, F32), _chk(dx, F32), _chk(idx, torch.int64)
+    M, d = x.shape
+    Q, C, _ = E.shape
+    assert x.stride(1) == 1 and dx.stride(1) == 1 and E.is_contiguous() and idx.shape == (M, Q) and idx.stride(1) == 1
+    assert g_out is None or (g_out.dtype == F32 and g_out.stride(1) == 1 and g_out.shape == (M, d))
+    assert coef is None or (coef.dtype == F32 and coef.is_contiguous() and coef.numel() == Q)
+    _lib.call('alm_rvq_train_bwd', x.data_ptr(), x.stride(0), idx.data_ptr(), idx.stride(0), E.data_ptr(), _p(g_out), g_out.stride(0) if g_out is not None else 0,
+              _p(coef), dx.data_ptr(), dx.stride(0), int(rotation), M, d, C, Q, _st())
+
+
 def bct_to_btc(x):
     B, C, T = x.shape
     out = _new((B, T, C), dtype=F32, device=x.device)

@@ -3,7 +3,9 @@
 return_codes_only=True)` -- the causal-conv encoder (soundstream.py:332-380, 519-531) and the eval-mode forward of the grouped residual VQ
 (soundstream.py:592-607, :840) -- and `decode_from_codebook_indices` / `decode` (soundstream.py:691-709: code lookup, transposed-conv
 decoder :347-360, 382-395, 615-627) run on the MI355X kernels of csrc/codec.hip (exact-fp32 MFMA).  Everything else the reference class
-does (discriminators, losses, train-mode RVQ, LFQ / FSQ quantizers) is out of scope and raises.  The conv encoder / decoder are
+does (discriminators, losses, LFQ / FSQ quantizers) is out of scope and raises.  In training mode the quantizer takes one
+training step per call (csrc/rvq_train.hip: quantize dropout, commitment loss, rotation trick, EMA codebooks with dead-code expiry, k-means
+initialisation; single process only), so `forward(x, return_recons_only=True | return_encoded=True)` is differentiable end to end.  The conv encoder / decoder are
 differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
 build a graph over the backward kernels of csrc/codec_bwd.hip and, for the LocalTransformer of use_local_attn=True, csrc/local_attn_bwd.hip (codec_bwd.py;
 attn_dim_head outside {32, 64} or a window outside the attention kernels' envelope raises there).
@@ -26,6 +28,7 @@ from __future__ import annotations
 
 import functools
 import os
+import random
 from itertools import cycle
 
 import torch
@@ -188,35 +191,156 @@ class _ResidualVQ(nn.Module):
 
 
 class GroupedResidualVQ(nn.Module):
-    """eval-mode forward of vector-quantize-pytorch's GroupedResidualVQ as the reference builds it (soundstream.py:592-607)."""
+    """vector-quantize-pytorch's GroupedResidualVQ as the reference builds it (soundstream.py:592-607).  eval(): the tokenize forward (alm_rvq_encode).
+    train(): one training step per call (csrc/rvq_train.hip; arithmetic restated in tests/rvq_train_restated.py) -- quantize dropout, per layer the
+    assignment against the pre-update codebook, commitment loss, rotation trick or straight-through output, and after the layer loop the EMA codebook
+    update with Laplace smoothing and dead-code expiry; layers whose `initted` is False are k-means-initialised on their residual first.  Codebooks get
+    no gradient (learnable_codebook=False); the input gradient is alm_rvq_train_bwd (codec_bwd.RvqTrainFn).  Single process only: with
+    torch.distributed at world size > 1 the training forward raises."""
 
-    def __init__(self, *, dim, groups=1, num_quantizers, codebook_size, **unused):
+    def __init__(self, *, dim, groups=1, num_quantizers, codebook_size, decay=0.95, commitment_weight=1., quantize_dropout=True,
+                 quantize_dropout_cutoff_index=1, quantize_dropout_multiple_of=1, rotation_trick=True, threshold_ema_dead_code=2, kmeans_iters=10, eps=1e-5,
+                 stochastic_sample_codes=False, **unused):
         super().__init__()
         assert dim % groups == 0
+        if stochastic_sample_codes:
+            raise NotImplementedError('stochastic_sample_codes is not implemented (reference default False)')
+        assert kmeans_iters >= 1 and quantize_dropout_cutoff_index >= 0 and quantize_dropout_multiple_of >= 1
         self.dim, self.groups, self.num_quantizers, self.codebook_size = dim, groups, num_quantizers, codebook_size
+        self.decay, self.commitment_weight, self.eps = decay, commitment_weight, eps
+        self.quantize_dropout = quantize_dropout and num_quantizers > 1
+        self.quantize_dropout_cutoff_index, self.quantize_dropout_multiple_of = quantize_dropout_cutoff_index, quantize_dropout_multiple_of
+        self.rotation_trick, self.threshold_ema_dead_code, self.kmeans_iters = rotation_trick, threshold_ema_dead_code, kmeans_iters
         self.rvqs = nn.ModuleList([_ResidualVQ(dim // groups, num_quantizers, codebook_size) for _ in range(groups)])
         self._packed = None
+        self._initted_cache = None
 
-    def _pack(self):
+    def _pack(self, require_init=True):
         embeds = [[l._codebook.embed for l in r.layers] for r in self.rvqs]
         ver = tuple((e.data_ptr(), core.tensor_version(e)) for row in embeds for e in row)
         if self._packed is None or self._packed[0] != ver:
             for r in self.rvqs:
                 for l in r.layers:
-                    if not bool(l._codebook.initted.item()):
-                        raise RuntimeError('codebooks are not initialised (`initted` is False): the k-means initialisation of the first training '
-                                           'batch (soundstream.py:600) is not part of the tokenize path -- load a trained codec or set them')
+                    if require_init and not bool(l._codebook.initted.item()):
+                        raise RuntimeError('codebooks are not initialised (`initted` is False): the k-means initialisation happens on the first '
+                                           'training-mode batch (soundstream.py:600) -- load a trained codec, set them, or run a training step')
             packs = []
             for row in embeds:
                 E = torch.stack([e[0].detach().to(F32) for e in row]).contiguous()       # [Q, C, d]
                 packs.append((E,) + ops.rvq_pack(E))
+            if not require_init:
+                return packs                                     # never cached: an eval call must still meet the check above
             self._packed = (ver, packs)
         return self._packed[1]
 
+    def _initted(self):
+        """[group][layer] bools of the `initted` buffers; read from the device only when one of them changed (tensor version)"""
+        bufs = [l._codebook.initted for r in self.rvqs for l in r.layers]
+        key = tuple((t.data_ptr(), core.tensor_version(t)) for t in bufs)
+        if self._initted_cache is None or self._initted_cache[0] != key:
+            flags = [bool(v) for v in torch.cat([t.reshape(1) for t in bufs]).tolist()]
+            q = self.num_quantizers
+            self._initted_cache = (key, [flags[g * q:(g + 1) * q] for g in range(self.groups)])
+        return self._initted_cache[1]
+
+    def sample_rows(self, num_rows, count, device):
+        """`count` random row numbers of `num_rows` (int64, on `device`): the k-means start points and the replacements of expired codes.  The one
+        place randomness enters the codebooks; override it for a fixed choice."""
+        if num_rows >= count:
+            return torch.randperm(num_rows, device=device)[:count]
+        return torch.randint(0, num_rows, (count,), device=device)
+
+    def dropout_index(self):
+        """index of the last active layer of this call: the grouped form of quantize dropout (one seed per call, shared by all groups), host only"""
+        q = self.num_quantizers
+        if not self.quantize_dropout:
+            return q - 1
+        seed = random.randint(0, int(1e7))
+        k = random.Random(seed).randrange(self.quantize_dropout_cutoff_index, q)
+        m = self.quantize_dropout_multiple_of
+        if m != 1:
+            k = -(-(k + 1) // m) * m - 1
+        return min(k, q - 1)
+
+    def _kmeans_init(self, resid, cb, E, Et, e2, q):
+        """k-means initialisation of one layer on its residual [M, d]: start from sampled rows, `kmeans_iters` rounds of (assign, per-code mean; an
+        empty cluster keeps its mean), then embed = means, cluster_size = the last round's counts, embed_avg = means * counts, initted = True"""
+        M, C = resid.shape[0], self.codebook_size
+        means = resid.index_select(0, self.sample_rows(M, C, resid.device)).unsqueeze(0).contiguous()       # [1, C, d]
+        for it in range(self.kmeans_iters):
+            ids = ops.rvq_encode(resid, means, *ops.rvq_pack(means))
+            n, s = ops.rvq_code_stats(resid, ids[:, 0], C)
+            last = it == self.kmeans_iters - 1
+            ops.rvq_kmeans_update(means[0], n, s, *((cb.embed, cb.embed_avg, cb.cluster_size) if last else ()))
+        cb.initted.fill_(True)
+        E[q].copy_(means[0])                                     # this step's pre-update codebook of the layer, and its distance image
+        Et1, e21 = ops.rvq_pack(E[q:q + 1])
+        Et[q].copy_(Et1[0]), e2[q].copy_(e21[0])
+
+    def train_step(self, x2, k):
+        """x2 fp32 [M, dim], k = last active layer -> (out [M, dim], losses [g, Q], idx [g, M, Q] (-1 on dropped layers), per group the pre-update
+        codebooks [Q, C, d]).  Updates the codebook buffers in place."""
+        M, dim = x2.shape
+        dg, Q, C = dim // self.groups, self.num_quantizers, self.codebook_size
+        dev = x2.device
+        for r in self.rvqs:
+            cb = r.layers[0]._codebook
+            if cb.embed.dtype != F32 or not cb.embed.is_cuda:
+                raise RuntimeError('train-mode GroupedResidualVQ needs fp32 codebook buffers on the GPU (no CPU fallback)')
+        out = torch.zeros((M, dim), dtype=F32, device=dev)
+        idx = torch.full((self.groups, M, Q), -1, dtype=torch.int64, device=dev)
+        losses = torch.zeros((self.groups, Q), dtype=F32, device=dev)
+        initted = self._initted()
+        thr = float(self.threshold_ema_dead_code)
+        snaps = []
+        for gi, (E, Et, e2) in enumerate(self._pack(require_init=False)):
+            xg, og = x2[:, gi * dg:(gi + 1) * dg], out[:, gi * dg:(gi + 1) * dg]
+            layers = self.rvqs[gi].layers
+            resid = torch.empty((M, dg), dtype=F32, device=dev)
+            resid.copy_(xg)
+            n_all = torch.empty((k + 1, C), dtype=F32, device=dev)
+            s_all = torch.empty((k + 1, C, dg), dtype=F32, device=dev)
+            for q in range(k + 1):
+                if not initted[gi][q]:
+                    self._kmeans_init(resid, layers[q]._codebook, E, Et, e2, q)
+                ops.rvq_encode(resid, E[q:q + 1], Et[q:q + 1], e2[q:q + 1], idx_out=idx[gi][:, q:q + 1])
+                ops.rvq_code_stats(resid, idx[gi][:, q], C, n_all[q], s_all[q])                      # of THIS layer's input residual
+                ops.rvq_train_quantize(resid, idx[gi][:, q], E[q], og, losses[gi, q:q + 1], self.commitment_weight / (M * dg), self.rotation_trick)
+            # EMA updates and expiries after the layer loop (neither influences a later layer of the same step)
+            dead = torch.empty((k + 1, 1 + C), dtype=torch.int32, device=dev)
+            for q in range(k + 1):
+                cb = layers[q]._codebook
+                ops.rvq_ema_update(cb.cluster_size, cb.embed_avg, cb.embed, n_all[q], s_all[q], self.decay, self.eps, thr, dead[q])
+            if thr > 0:
+                counts = dead[:, 0].tolist()                     # the ONE host read per group and step: the dead-code counts size the row sampling
+                for q, cnt in enumerate(counts):
+                    if cnt:
+                        cb = layers[q]._codebook
+                        ops.rvq_expire(dead[q, 1:], cnt, self.sample_rows(M, cnt, dev).to(torch.int64).contiguous(), xg, idx[gi], E, q, self.rotation_trick, thr,
+                                       cb.cluster_size, cb.embed_avg, cb.embed)
+            snaps.append(E)
+        self._packed = None                                      # the kernels write through raw pointers: no tensor version moved
+        return out, losses, idx, snaps
+
+    def _forward_train(self, x):
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise NotImplementedError('train-mode GroupedResidualVQ is single-process: the all-reduce of the per-code statistics (cluster sizes, embedding '
+                                      'sums) and the distributed k-means initialisation are not implemented')
+        if not x.is_cuda:
+            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
+        b, n, dim = x.shape
+        x2 = x.reshape(b * n, dim).to(F32).contiguous()
+        k = self.dropout_index()
+        if codec_bwd.wants_grad(self, x2):
+            out, losses, idx = codec_bwd.RvqTrainFn.apply(x2, self, k)
+        else:
+            out, losses, idx, _ = self.train_step(x2.detach(), k)
+        return out.view(b, n, dim), idx.view(self.groups, b, n, self.num_quantizers), losses
+
     def forward(self, x):
-        """x fp32 (b, n, dim) -> (quantized (b, n, dim), indices (g, b, n, q) int64, commit_loss zeros (g, q))."""
+        """x fp32 (b, n, dim) -> (quantized (b, n, dim), indices (g, b, n, q) int64, commit_loss (g, q): zeros in eval mode)."""
         if self.training:
-            raise NotImplementedError('only the eval-mode forward (tokenize) is implemented')
+            return self._forward_train(x)
         b, n, dim = x.shape
         x2 = x.reshape(b * n, dim).to(F32).contiguous()
         dg = dim // self.groups
@@ -446,7 +570,11 @@ class SoundStream(nn.Module):
         self.codebook_dim = codebook_dim
         self.rq_groups = rq_groups
         self.codebook_size = codebook_size
-        self.rq = GroupedResidualVQ(dim=codebook_dim, num_quantizers=rq_num_quantizers, codebook_size=codebook_size, groups=rq_groups)
+        self.rq = GroupedResidualVQ(dim=codebook_dim, num_quantizers=rq_num_quantizers, codebook_size=codebook_size, groups=rq_groups, decay=rq_ema_decay,
+                                    commitment_weight=rq_commitment_weight, quantize_dropout=True,
+                                    quantize_dropout_cutoff_index=kwargs.get('quantize_dropout_cutoff_index', 1),
+                                    quantize_dropout_multiple_of=rq_quantize_dropout_multiple_of, rotation_trick=rq_rotation_trick, kmeans_iters=10,
+                                    threshold_ema_dead_code=2)                                           # soundstream.py:592-607 (rq_kwargs: ignored, like before)
         self.eval()
 
     @property
@@ -491,27 +619,29 @@ class SoundStream(nn.Module):
         self.eval()
         return self.forward(audio, return_codes_only=True)
 
-    @torch.no_grad()
     def forward(self, x, target=None, is_denoising=None, return_encoded=False, return_codes_only=False, return_discr_loss=False,
                 return_discr_losses_separately=False, return_loss_breakdown=False, return_recons_only=False, input_sample_hz=None,
                 apply_grad_penalty=False, curtail_from_left=False):
-        """The eval-mode branches of soundstream.py:802-862 (same positional order): return_codes_only -> indices (g, b, n, q);
-        return_encoded -> (quantized, indices 'b n (g q)', commit_loss); return_recons_only -> the reconstructed wave.  The training
-        branches (discriminators, losses) are out of scope."""
+        """The codec branches of soundstream.py:802-862 (same positional order): return_codes_only -> indices (g, b, n, q);
+        return_encoded -> (quantized, indices 'b n (g q)', commit_loss (g, q)); return_recons_only -> the reconstructed wave.  In eval mode
+        nothing is recorded for autograd and commit_loss is zero; in training mode the quantizer takes one training step (GroupedResidualVQ) and,
+        with grad mode on, the results carry a graph through encoder, quantizer and decoder.  The loss branches (discriminators, adversarial /
+        feature / mel losses) are out of scope and raise."""
         if target is not None or is_denoising is not None or return_discr_loss or return_discr_losses_separately or return_loss_breakdown \
                 or apply_grad_penalty or not (return_encoded or return_codes_only or return_recons_only):
-            raise NotImplementedError('only the eval-mode branches forward(..., return_codes_only=True | return_encoded=True | '
-                                      'return_recons_only=True) are implemented (SoundStream training is out of scope)')
-        x, lead = self.process_input(x, input_sample_hz=input_sample_hz, curtail_from_left=curtail_from_left)
-        feats = self.encode(x)
-        quantized, indices, commit_loss = self.rq(feats)
-        if return_codes_only:
-            return indices                                       # (g, b, n, q), soundstream.py:847-848
-        b, n = indices.shape[1], indices.shape[2]
-        if return_encoded:
-            return quantized, indices.permute(1, 2, 0, 3).reshape(b, n, -1), commit_loss          # 'g b n q -> b n (g q)', :851
-        recon = self.decode(quantized)                           # :857-866, unpack(recon_x, ps, '* c n')
-        return recon.reshape(*lead, recon.shape[-2], recon.shape[-1])
+            raise NotImplementedError('only forward(..., return_codes_only=True | return_encoded=True | return_recons_only=True) is implemented '
+                                      '(the discriminators and the losses of SoundStream training are out of scope)')
+        with torch.set_grad_enabled(torch.is_grad_enabled() and self.training):
+            x, lead = self.process_input(x, input_sample_hz=input_sample_hz, curtail_from_left=curtail_from_left)
+            feats = self.encode(x)
+            quantized, indices, commit_loss = self.rq(feats)
+            if return_codes_only:
+                return indices                                       # (g, b, n, q), soundstream.py:847-848
+            b, n = indices.shape[1], indices.shape[2]
+            if return_encoded:
+                return quantized, indices.permute(1, 2, 0, 3).reshape(b, n, -1), commit_loss          # 'g b n q -> b n (g q)', :851
+            recon = self.decode(quantized)                           # :857-866, unpack(recon_x, ps, '* c n')
+            return recon.reshape(*lead, recon.shape[-2], recon.shape[-1])
 
     def decode_from_codebook_indices(self, quantized_indices):               # soundstream.py:691-699
         assert quantized_indices.dtype in (torch.long, torch.int32)

@@ -393,6 +393,38 @@ int alm_rvq_pack(const float* E, float* Et, float* e2, int Q, int C, int d, void
 int alm_rvq_encode(const float* x, long long ldx, const float* E, const float* Et, const float* e2, long long* idx, long long ldi, float* quant,
                    long long ldq, int T, int d, int C, int Q, void* stream);
 int alm_bct_to_btc(const float* in, float* out, int B, int C, int T, void* stream);   /* 'b c n -> b n c', soundstream.py:823 */
+/* ---- train-mode residual VQ (csrc/rvq_train.hip; soundstream.py:592-607: EMA codebooks, commitment loss, rotation trick, dead-code expiry, k-means
+ * init; restated in tests/rvq_train_restated.py).  fp32, no float atomics: every output is bitwise reproducible.  The assignment stays on alm_rvq_encode
+ * (one quantizer per call on the current residual).  Rows r / x / out / g_out / dx are [M][ld*] column views of one group (d columns), idx an int64
+ * column ([M] with stride ldi; -1 or a value outside [0, C) = the row takes no part), E one layer's [C][d] or all layers' [Q][C][d] codebooks.
+ *   alm_rvq_code_stats     : n [C] = rows per code (as floats), s [C][d] = their sums: stable counting sort of the rows by code, then a code's rows
+ *                            are added in ascending row order in chunks of alm_rvq_code_stats_chunk() rows, the chunks' partials in chunk order; codes
+ *                            without rows get n = 0, s = 0.  ws: alm_rvq_code_stats_ws_floats(M, d, C) 4-byte words (-1: too large).  C <= 8192.
+ *   alm_rvq_train_quantize : one layer, in place: quant = E[idx]; y = rotate_to(r, quant) (rotation) or r + (quant - r); resid -= y; out += y;
+ *                            loss[0] = loss_scale * sum over rows of |quant - r|^2, reduced in a fixed order through part
+ *                            (alm_rvq_train_quantize_blocks(M) floats).  d <= 1024, else ALM_ERR_UNSUPPORTED (also _expire / _bwd).
+ *   alm_rvq_ema_update     : cluster_size = cluster_size * decay + n * (1 - decay); embed_avg likewise from s; embed = embed_avg / smoothed with
+ *                            smoothed = (cluster_size + eps) / (sum + C eps) * sum, the sum over C in a fixed order (total: one float of workspace).
+ *                            dead int [1 + C]: the number of codes with cluster_size < threshold after the update, then those codes, ascending.
+ *   alm_rvq_expire         : for i < count: code dead[i] gets embed = the layer-q residual of row rows[i] (recomputed from x, the saved idx [M][ldi]
+ *                            and the pre-update codebooks E [Q][C][d]), embed_avg = threshold * that row, cluster_size = threshold.
+ *   alm_rvq_kmeans_update  : means = n == 0 ? means : s / max(n, 1); with embed != NULL also embed = means, embed_avg = means * n, cluster_size = n.
+ *   alm_rvq_train_bwd      : dx = sum over the layers of (dy / dr)^T g_out + coef[q] (r_q - quant_q), every row's chain recomputed from x, idx
+ *                            [M][ldi] (Q columns) and the pre-update codebooks E [Q][C][d] with the forward's own arithmetic.  g_out / coef may be NULL. */
+int alm_rvq_code_stats_chunk(void);
+int alm_rvq_code_stats_ws_floats(int M, int d, int C);
+int alm_rvq_code_stats(const float* r, long long ldr, const long long* idx, long long ldi, float* n, float* s, float* ws, long long ws_floats, int M, int d,
+                       int C, void* stream);
+int alm_rvq_train_quantize_blocks(int M);
+int alm_rvq_train_quantize(float* resid, long long ldr, const long long* idx, long long ldi, const float* E, float* out, long long ldo, float* loss,
+                           float* part, float loss_scale, int rotation, int M, int d, int C, void* stream);
+int alm_rvq_ema_update(float* cluster_size, float* embed_avg, float* embed, const float* n, const float* s, float decay, float eps, float threshold,
+                       int* dead, float* total, int C, int d, void* stream);
+int alm_rvq_expire(const int* dead, int count, const long long* rows, const float* x, long long ldx, const long long* idx, long long ldi, const float* E,
+                   int q, int rotation, float threshold, float* cluster_size, float* embed_avg, float* embed, int M, int d, int C, void* stream);
+int alm_rvq_kmeans_update(float* means, const float* n, const float* s, float* embed, float* embed_avg, float* cluster_size, int C, int d, void* stream);
+int alm_rvq_train_bwd(const float* x, long long ldx, const long long* idx, long long ldi, const float* E, const float* g_out, long long ldg,
+                      const float* coef, float* dx, long long lddx, int rotation, int M, int d, int C, int Q, void* stream);
 /* backward of the codec's conv stacks (csrc/codec_bwd.hip), exact fp32 on the matrix core, no float atomics (bitwise reproducible).  g = dL/dout
  * [B][Cout][Tout]; y = the saved post-ELU output of the conv (same shape) or NULL: g is read as g * (y > 0 ? 1 : y + 1) (ELU backward fused into
  * the load).  Shapes, pad and zero_pad as in alm_conv1d_causal.

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train]"""
 import os
 import sys
 import time
@@ -616,6 +616,63 @@ def bench_t5():
         print(f't5 v1.1-base {B} x {T}: native {nat[0]:.3f} ms (min {nat[1]:.3f}, max {nat[2]:.3f}; {flop / nat[0] / 1e9:.1f} TFLOP/s, '
               f'{nat[0] / floor:.2f} x the {floor:.3f} ms fp32 matrix-peak floor)   eager torch fp32 {ref[0]:.3f} ms (min {ref[1]:.3f}, max {ref[2]:.3f})   '
               f'native / eager {nat[0] / ref[0]:.2f}   max rel diff {err:.1e}')
+
+
+def bench_rvq_train():
+    """train-mode residual VQ at the workload shape (8 x 30 s @ 24 kHz: M = 18 000 frames, d = 512, C = 1024, Q = 8, one group): the training forward
+    (all layers active, no init step), the per-code statistics kernel alone (uniform codes, and 90 % of the rows on four codes), the backward, the eval
+    alm_rvq_encode of the same shape, and as a yardstick the dense formulation the reference runs for the statistics -- einsum('nd,nc->cd') with the
+    one-hot matrix plus its column sum -- in ATen fp32 on the same GPU.  Median of 20 after 3 warm-up runs, one event pair per call."""
+    from audiolm_pytorch_amd import soundstream as S
+    M, d, C, Q = 18000, 512, 1024, 8
+
+    def median_ms(fn, iters=20, warm=3):
+        for _ in range(warm):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        return ts[len(ts) // 2]
+    torch.manual_seed(0)
+    rq = S.GroupedResidualVQ(dim=d, num_quantizers=Q, codebook_size=C, quantize_dropout=False)
+    for q, l in enumerate(rq.rvqs[0].layers):
+        cb = l._codebook
+        cb.embed.copy_(torch.randn(1, C, d) * 0.7 ** q), cb.cluster_size.fill_(M / C), cb.embed_avg.copy_(cb.embed * (M / C)), cb.initted.fill_(True)
+    rq = rq.to(dev)
+    x = torch.randn(1, M, d, device=dev)
+    rq.eval()
+    with torch.no_grad():
+        t_eval = median_ms(lambda: rq(x))
+    rq.train()
+    with torch.no_grad():
+        t_fwd = median_ms(lambda: rq(x))
+    xg = x.clone().requires_grad_()
+    out, _, losses = rq(xg)
+    g = torch.randn_like(out)
+    t_bwd = median_ms(lambda: torch.autograd.grad([out, losses], [xg], [g, torch.ones_like(losses)], retain_graph=True))
+    r = x[0]
+    for name, idx in (('uniform codes', torch.randint(0, C, (M,), device=dev)),
+                      ('90 % of the rows on 4 codes', torch.where(torch.rand(M, device=dev) < 0.9, torch.randint(0, 4, (M,), device=dev), torch.randint(0, C, (M,), device=dev)))):
+        t_stats = median_ms(lambda: ops.rvq_code_stats(r, idx, C))
+
+        def dense():
+            onehot = torch.nn.functional.one_hot(idx, C).to(F32)
+            return torch.einsum('nd,nc->cd', r, onehot), onehot.sum(0)
+        t_dense = median_ms(dense)
+        n, s = ops.rvq_code_stats(r, idx, C)
+        rs, rn = dense()
+        print(f'rvq_train stats {M} x {d} -> {C} codes, {name}: {t_stats:.3f} ms ({(M * d + C * d) * 4 / t_stats / 1e6:.0f} GB/s of rows + sums)   '
+              f'dense one-hot einsum + sum in ATen fp32 {t_dense:.3f} ms ({2 * C * M * d / t_dense / 1e9:.1f} TFLOP/s)   ratio {t_dense / t_stats:.1f}   '
+              f'counts equal {bool(torch.equal(n, rn))}  max rel diff of the sums {relerr(s, rs):.1e}')
+    print(f'rvq_train forward {M} frames x {Q} x {C} codes, d {d}: {t_fwd:.2f} ms   eval alm_rvq_encode {t_eval:.2f} ms   forward / eval {t_fwd / t_eval:.2f}   '
+          f'backward {t_bwd:.2f} ms')
 
 
 if __name__ == '__main__':
