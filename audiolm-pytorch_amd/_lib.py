@@ -29,6 +29,10 @@ SIGNATURES = {
     'alm_gemm_bf16_nt_splitk': [_P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _L, _L, _L, _F, _I, _P],
     'alm_gemm_bf16_tn_splitk': [_P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _L, _L, _L, _F, _I, _P],
     'alm_gemm_bf16_tn_batched': [_P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _I, _L, _L, _L, _L, _L, _L, _F, _I, _P],
+    'alm_gemm_bf16_tn_batched_panels': [_P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _I, _L, _L, _L, _L, _L, _L, _F, _I, _P, _P],
+    'alm_gemm_bf16_tn_grouped': [_P, _I, _P, _I, _P],
+    'alm_gemm_tn_grouped_plan': [_P, _I, _I, _P],
+    'alm_gemm_tn_grouped_ws_floats': [_P, _I, _I],
     'alm_gemm_bf16_nt_group2': [_P, _P, _P, _I, _I, _I, _L, _L, _L, _P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _P],
     'alm_gemm_bf16_nt_tile': [_P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _F, _I, _I, _I, _P],
     'alm_transpose_bf16': [_P, _P, _I, _I, _L, _L, _I, _P],
@@ -217,6 +221,13 @@ class AlmPackJob(ctypes.Structure):
     """mirror of AlmPackJob in include/audiolm_hip.h"""
     _fields_ = [('src', c_void_p), ('rows', c_int), ('cols', c_int), ('ld_src', c_longlong), ('dst', c_void_p), ('ld_dst', c_longlong),
                 ('rows_pad', c_int), ('cols_pad', c_int), ('dstT', c_void_p), ('ld_dstT', c_longlong)]
+
+
+class AlmTnJob(ctypes.Structure):
+    """mirror of AlmTnJob in include/audiolm_hip.h (16 eight-byte words; the launch-list recorder relocates the c_void_p ones)"""
+    _fields_ = [('At', c_void_p), ('Bt', c_void_p), ('C', c_void_p), ('M', c_int), ('N', c_int), ('K', c_int), ('nb1', c_int), ('nb2', c_int),
+                ('accumulate', c_int), ('alpha', c_float), ('reserved', c_int), ('lda', c_longlong), ('ldb', c_longlong), ('ldc', c_longlong),
+                ('sA1', c_longlong), ('sA2', c_longlong), ('sB1', c_longlong), ('sB2', c_longlong), ('sC1', c_longlong), ('sC2', c_longlong)]
 
 
 _BOUND = {}          # name -> bound ctypes function (one dict lookup per call instead of load() + getattr on the CDLL: ~150 calls per training step)

@@ -853,11 +853,18 @@ def stack_backward(dhn, mask_u8, flat, cfg: StackCfg, cache: WeightCache, saved,
                             dWq=lambda a, b: (bst['dQ'][a:b].unsqueeze(1), stk['XNat'][a:b].unsqueeze(1)),                                         # dWq = dQ^T @ XN
                             dWkv=lambda a, b: (bst['dKV'][a:b].unsqueeze(1), stk['Xat'][a:b].unsqueeze(1)))                                        # dWkv = dKV^T @ X
             jobs = [operands[k](l0, l1) + (wgg[k],) for k in kinds] + [operands[k](0, L) + (wgg[k],) for k in late_kinds]
+            # one group at the end, no hook: every kind launches only the panels that fill whole rounds of the chip; what is left of all kinds (the hybrid
+            # plan's tails, the small kinds whole) is ONE grouped launch + one reduce after the last kind (ops.TN_GROUPED, ops.gemm_tn_grouped)
+            left = [] if (ops.TN_GROUPED and ngroups == 1 and on_layer_grads is None) else None
             for At, Bt, C in jobs:
                 if ngroups > 1 or on_layer_grads is not None:  # (with a gradient hook even a single group goes to the side stream: its bucket follows it there)
                     side.run(lambda At=At, Bt=Bt, C=C: ops.gemm_tn_batched(At, Bt, C), At, Bt, C)
+                elif left is not None:
+                    ops.gemm_tn_batched(At, Bt, C, leftovers=left)
                 else:                                          # one group at the end: nothing left to run beside it -- the main stream, no fork / join
                     ops.gemm_tn_batched(At, Bt, C)             # (interleaved A/B: 13.11 -> 12.97 ms/step)
+            if left:
+                ops.gemm_tn_grouped(left)
             for k in kinds:
                 for l in range(l0, l1):
                     g_ = wgg[k][l - l0]

@@ -65,6 +65,7 @@ struct GemmParams {
     int raster;        // 1: split-K launches -- 1-D grid, XCD-panel rasterisation (see kernel): panel q on XCD q % 8.  2: the same with panel q on
                        // XCD q / (P / 8) -- consecutive panels are the row blocks of ONE problem, so an XCD then needs the small operand of 2-3
                        // problems instead of every problem's (batched weight gradients: the small operand was fetched by all 8 XCD L2s)
+                       // 3 (staggered tile only): the launching kernel hands over (tile row | tile column << 16, problem, K slice) itself
     int nsl;           // number of K slices (raster 1)
     int nbt = 0;       // total number of batched problems nb1 * nb2 (0: nb2 -- the one-level callers); raster 1 enumerates panels over all of them
     int plimit = 0;    // raster 1: > 0 = launch only the first `plimit` panels (alm_gemm_bf16_tn_batched: whole waves at full K, the tail separately)
@@ -509,7 +510,12 @@ __device__ __forceinline__ void gemm_stag_body(const GemmParams& p, const int bx
 
     const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
     int tm, tn, zb, zs;
-    if (p.raster >= 1) {                                                    // split-K weight gradients: XCD-panel rasterisation (see gemm_kernel)
+    if (p.raster == 3) {                                                    // the caller placed the workgroup itself (gemm_tn_grouped_kernel)
+        tm = bx & 0xffff;
+        tn = bx >> 16;
+        zb = by;
+        zs = bz;
+    } else if (p.raster >= 1) {                                             // split-K weight gradients: XCD-panel rasterisation (see gemm_kernel)
         const int L = bx, xcd = L & 7, j = L >> 3;
         const bool m_major = tiles_m >= tiles_n;
         const int tmaj = m_major ? tiles_m : tiles_n, Q = m_major ? tiles_n : tiles_m;
@@ -802,6 +808,92 @@ __global__ __launch_bounds__(512) void gemm_stag_group2_kernel(GemmParams p0, Ge
     const bool second = (int)blockIdx.x >= tiles0;
     const GemmParams& p = second ? p1 : p0;
     gemm_stag_body<TNMODE, OUT_F32>(p, second ? (int)blockIdx.x - tiles0 : (int)blockIdx.x, 0, 0);
+}
+
+// ---- grouped weight-gradient leftovers (alm_gemm_bf16_tn_grouped): the 256 x 256 tiles of up to 8 batched TN jobs, each cut into the same S K-slices, in ONE
+// launch of the staggered TN body.  The UNIT of placement is (problem, slice): all tiles of one problem over one K slice -- they share that slice of both
+// operands, so a unit's workgroups sit next to one another on ONE XCD (one L2).  Units are numbered job by job, u = base[j] + problem * S + slice, and dealt
+// round-robin over the 8 XCDs (unit u on XCD u % 8; workgroup b runs on XCD b % 8 and is slot b / 8 of that XCD's list), which balances the XCDs to within one
+// unit per job.  Every workgroup finds its (job, problem, slice, tile) from the small table below: scalar arithmetic, no memory but the kernel arguments.
+constexpr int TN_GROUP_MAX = 8;
+struct TnGroupTable {
+    GemmParams p[TN_GROUP_MAX];
+    int tiles[TN_GROUP_MAX];            // tiles of ONE problem of the job (tiles_m x tiles_n)
+    int tiles_n[TN_GROUP_MAX];
+    int nunits[TN_GROUP_MAX];           // problems x S
+    int base[TN_GROUP_MAX];             // first unit number of the job
+    int njobs, S;
+};
+static_assert(sizeof(TnGroupTable) <= 3800, "kernel-argument segment");
+
+// workgroups of XCD x's list that belong to a job whose units are [base, base + n): those numbered == x (mod 8); `first` = the lowest of them
+__host__ __device__ __forceinline__ int tn_group_units_on(int base, int n, int x, int* first) {
+    const int f = base + ((x - base) & 7);
+    *first = f;
+    return f < base + n ? (base + n - 1 - f) / 8 + 1 : 0;
+}
+
+__global__ __launch_bounds__(512) void gemm_tn_grouped_kernel(TnGroupTable g) {
+    const int x = (int)blockIdx.x & 7;
+    int slot = (int)blockIdx.x >> 3, j = 0, first = 0;
+    for (; j < g.njobs; ++j) {
+        const int pieces = tn_group_units_on(g.base[j], g.nunits[j], x, &first) * g.tiles[j];
+        if (slot < pieces) break;
+        slot -= pieces;
+    }
+    if (j >= g.njobs) return;                                               // whole workgroup (the shorter XCD lists)
+    const int v = first + 8 * (slot / g.tiles[j]) - g.base[j], t = slot % g.tiles[j];
+    gemm_stag_body<true, true>(g.p[j], (t / g.tiles_n[j]) | ((t % g.tiles_n[j]) << 16), v / g.S, v % g.S);
+}
+
+// second stage: C[job][problem] (+)= alpha * sum over slices, in slice order (blockIdx.y = problem over all jobs)
+struct TnReduceJob {
+    const float* ws;
+    float* C;
+    long long mn, slice_stride, ldc, sC1, sC2;
+    int N, nb2, accumulate;
+    float alpha;
+};
+struct TnReduceTable {
+    TnReduceJob j[TN_GROUP_MAX];
+    int first[TN_GROUP_MAX + 1];        // first blockIdx.y of every job
+    int njobs, S;
+};
+
+__global__ __launch_bounds__(256) void tn_grouped_reduce_kernel(TnReduceTable tb) {
+    int ji = 0;
+    while (ji + 1 < tb.njobs && (int)blockIdx.y >= tb.first[ji + 1]) ++ji;
+    const TnReduceJob& q = tb.j[ji];
+    const int zb = (int)blockIdx.y - tb.first[ji];
+    const float* __restrict__ ws = q.ws + (long long)zb * q.mn;
+    float* __restrict__ C = q.C + (long long)(zb / q.nb2) * q.sC1 + (long long)(zb % q.nb2) * q.sC2;
+    const long long mn = q.mn, stride = q.slice_stride, ldc = q.ldc;
+    const int N = q.N, S = tb.S, accumulate = q.accumulate;
+    const float alpha = q.alpha;
+    const bool vec = (N & 3) == 0 && (ldc & 3) == 0 && ((uintptr_t)C & 15) == 0 && ((uintptr_t)ws & 15) == 0 && (mn & 3) == 0 && (stride & 3) == 0;
+    if (vec) {
+        const long long mn4 = mn >> 2;
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < mn4; i += (long long)gridDim.x * 256) {
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int z = 0; z < S; ++z) {
+                const float4 w = *reinterpret_cast<const float4*>(ws + (long long)z * stride + i * 4);
+                s.x += w.x; s.y += w.y; s.z += w.z; s.w += w.w;
+            }
+            s.x *= alpha; s.y *= alpha; s.z *= alpha; s.w *= alpha;
+            const long long e = i * 4, m = e / N, n = e % N;
+            float4* c = reinterpret_cast<float4*>(C + m * ldc + n);
+            if (accumulate) { const float4 w = *c; s.x += w.x; s.y += w.y; s.z += w.z; s.w += w.w; }
+            *c = s;
+        }
+        return;
+    }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < mn; i += (long long)gridDim.x * 256) {
+        float s = 0.f;
+        for (int z = 0; z < S; ++z) s += ws[(long long)z * stride + i];
+        s *= alpha;
+        float* c = C + (i / N) * ldc + i % N;
+        *c = accumulate ? *c + s : s;
+    }
 }
 
 // ---- 256 x 256 x 64, FOUR waves (one per SIMD), wave tile 128 x 128 (tile id 14; NT and TN) -----------------------------------------------
@@ -1625,6 +1717,117 @@ int splitk_fixed(const bf16_t* At, const bf16_t* Bt, float* C, float* ws, int M,
     return 0;
 }
 
+// step (a) of the hybrid plan: the first hy.panels_a panels (whole rounds of the chip) at full K, straight into C -- no partials, no reduce
+int hybrid_panels_launch(const void* At, const void* Bt, float* C, int M, int N, int K, long long lda, long long ldb, long long ldc, int nb1, int nb2, long long sA1,
+                         long long sA2, long long sB1, long long sB2, long long sC1, long long sC2, float alpha, int accumulate, const HybridPlan& hy, hipStream_t st) {
+    static const int raster_a = [] { const char* e = getenv("ALM_GEMM_HYBRID_RASTER"); return e ? atoi(e) : 2; }();    // A/B switch: 1 = round-robin panels
+    GemmParams pa{(const bf16_t*)At, (const bf16_t*)Bt, C, nullptr, M, N, K, lda, ldb, ldc, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, 0, 0,
+                  (hy.panels_a % 8 == 0 && raster_a == 2) ? 2 : 1, 1, nb1 * nb2, hy.panels_a};
+    return launch_gemm<true>(pa, nb1 * nb2, 1, 1, 13, st, true, true);
+}
+
+// the tail of the hybrid plan as a problem of its own: the last problem's remaining row (column) blocks
+AlmTnJob hybrid_tail(const void* At, const void* Bt, float* C, int M, int N, int K, long long lda, long long ldb, long long ldc, int nb1, int nb2, long long sA1,
+                     long long sA2, long long sB1, long long sB2, long long sC1, long long sC2, float alpha, int accumulate, const HybridPlan& hy) {
+    const long long zA = (long long)(nb1 - 1) * sA1 + (long long)(nb2 - 1) * sA2, zB = (long long)(nb1 - 1) * sB1 + (long long)(nb2 - 1) * sB2;
+    const long long zC = (long long)(nb1 - 1) * sC1 + (long long)(nb2 - 1) * sC2;
+    return AlmTnJob{(const bf16_t*)At + zA + (hy.m_major ? hy.off : 0), (const bf16_t*)Bt + zB + (hy.m_major ? 0 : hy.off),
+                    C + zC + (hy.m_major ? (long long)hy.off * ldc : hy.off), hy.m_major ? M - hy.off : M, hy.m_major ? N : N - hy.off, K, 1, 1, accumulate, alpha, 0,
+                    lda, ldb, ldc, 0, 0, 0, 0, 0, 0};
+}
+
+// ---- plan of the grouped leftover launch (gemm_tn_grouped_kernel) ------------------------------------------------------------------------------------
+// ONE slice count S for all jobs, from a time model in the form of the measured NT one (docs/LABBOOK.md round 6, item 2: us = 9.0 + 1.52 ksteps + 18.1 (S > 1) + 2.6 S per
+// launch of one resident round), re-fitted to this launch at the headline's leftovers (144 tiles, K = 16384, S = 1 .. 10; docs/LABBOOK.md round 7):
+//   t(S) = full rounds x (TNG_ROUND_US + TNG_KSTEP_US x kps)  +  last, partial round: TNG_ROUND_US + kps x (TNG_KSTEP_LO_US + (TNG_KSTEP_US - TNG_KSTEP_LO_US) x f)
+//          +  [S > 1]  (TNG_PUBLISH_US + (S + 1) x leftover bytes / TNG_REDUCE_BPUS)
+// kps = K-steps per slice; rounds = the busiest XCD's workgroups / its 32 CUs, f = the filled fraction of the last one (a K-step of a 256 x 256 workgroup takes
+// 1.2 us on a nearly empty chip and 1.9 us on a full one: a part-filled last round is cheaper than a whole one).  Reproduces the ten measured totals to 7 %
+// and their order (S = 5 at the headline shape).  Slices are whole K-steps, none empty, at least 4 K-steps each.
+constexpr double TNG_ROUND_US = 9.0, TNG_KSTEP_US = 1.92, TNG_KSTEP_LO_US = 1.2, TNG_PUBLISH_US = 18.1, TNG_REDUCE_BPUS = 5.8e6;
+struct TnGroupPlan { int tiles, S, kps, pieces, blocks, rounds; long long ws_floats; int longest; };
+
+bool tn_job_live(const AlmTnJob& j) { return j.M > 0 && j.N > 0 && j.nb1 > 0 && j.nb2 > 0; }
+
+int tn_jobs_check(const AlmTnJob* jobs, int njobs) {
+    if (njobs < 0 || njobs > TN_GROUP_MAX || (njobs > 0 && !jobs)) return ALM_ERR_BAD_ARG;
+    int K = 0;
+    for (int i = 0; i < njobs; ++i) {
+        const AlmTnJob& j = jobs[i];
+        if (!tn_job_live(j)) continue;
+        if (j.K <= 0 || (K && j.K != K)) return ALM_ERR_BAD_ARG;            // one contraction length per call
+        K = j.K;
+        if ((j.lda & 7) || (j.ldb & 7) || ((j.sA1 | j.sA2 | j.sB1 | j.sB2) & 7) || ((uintptr_t)j.At & 15) || ((uintptr_t)j.Bt & 15)) return ALM_ERR_BAD_ARG;
+        if (view_too_big(j.K, j.lda) || view_too_big(j.K, j.ldb)) return ALM_ERR_UNSUPPORTED;
+        if ((long long)j.nb1 * j.nb2 > 4096 || j.M > (1 << 23) || j.N > (1 << 23)) return ALM_ERR_UNSUPPORTED;
+    }
+    return 0;
+}
+
+// geometry of the launch for a GIVEN S: fills tiles / pieces / blocks / rounds / ws_floats (and the table's placement arrays when tb != nullptr)
+void tn_group_geometry(const AlmTnJob* jobs, int njobs, int S, TnGroupPlan* pl, TnGroupTable* tb) {
+    int base = 0, nj = 0, tiles = 0;
+    int b_[TN_GROUP_MAX], n_[TN_GROUP_MAX], t_[TN_GROUP_MAX];
+    long long wsf = 0;
+    for (int i = 0; i < njobs; ++i) {
+        const AlmTnJob& j = jobs[i];
+        if (!tn_job_live(j)) continue;
+        const int tm = (j.M + 255) / 256, tn = (j.N + 255) / 256, nbt = j.nb1 * j.nb2;
+        b_[nj] = base; n_[nj] = nbt * S; t_[nj] = tm * tn;
+        if (tb) { tb->tiles[nj] = tm * tn; tb->tiles_n[nj] = tn; tb->nunits[nj] = nbt * S; tb->base[nj] = base; }
+        base += nbt * S;
+        tiles += tm * tn * nbt;
+        if (S > 1) wsf += ((long long)S * nbt * j.M * j.N + 3) & ~3LL;      // (every job's partials start 16-byte aligned)
+        ++nj;
+    }
+    int longest = 0;
+    for (int x = 0; x < 8; ++x) {
+        int len = 0, first;
+        for (int k = 0; k < nj; ++k) len += tn_group_units_on(b_[k], n_[k], x, &first) * t_[k];
+        longest = len > longest ? len : longest;
+    }
+    pl->tiles = tiles; pl->S = S; pl->pieces = tiles * S; pl->blocks = 8 * longest; pl->rounds = (longest + 31) / 32; pl->ws_floats = wsf; pl->longest = longest;
+    if (tb) { tb->njobs = nj; tb->S = S; }
+}
+
+// K-steps per slice when K is cut into S slices of whole K-steps, or 0 when that leaves a slice empty
+int tn_group_kps(int K, int S) {
+    const int ksteps = (K + BK - 1) / BK, kps = (ksteps + S - 1) / S;
+    return (ksteps + kps - 1) / kps == S ? kps : 0;
+}
+
+TnGroupPlan tn_group_plan(const AlmTnJob* jobs, int njobs, int slices) {
+    TnGroupPlan best{0, 1, 0, 0, 0, 0, 0, 0};
+    int K = 0;
+    double elems = 0.;
+    for (int i = 0; i < njobs; ++i)
+        if (tn_job_live(jobs[i])) { K = jobs[i].K; elems += (double)jobs[i].nb1 * jobs[i].nb2 * jobs[i].M * jobs[i].N; }
+    if (K == 0) return best;
+    if (slices > 0) {                                                       // forced: the nearest count at or below it that leaves no slice empty
+        int S = slices;
+        while (S > 1 && tn_group_kps(K, S) == 0) --S;
+        tn_group_geometry(jobs, njobs, S, &best, nullptr);
+        best.kps = tn_group_kps(K, S);
+        return best;
+    }
+    double best_t = 1e30;
+    for (int S = 1; S <= 32; ++S) {
+        const int kps = tn_group_kps(K, S);
+        if (kps == 0 || (S > 1 && kps < 4)) continue;
+        TnGroupPlan pl;
+        tn_group_geometry(jobs, njobs, S, &pl, nullptr);
+        pl.kps = kps;
+        if (pl.ws_floats > 0x7fffffffLL) break;
+        const int full = pl.longest / 32;
+        const double f = (pl.longest % 32) / 32.0;
+        double t = full * (TNG_ROUND_US + TNG_KSTEP_US * kps);
+        if (f > 0.) t += TNG_ROUND_US + kps * (TNG_KSTEP_LO_US + (TNG_KSTEP_US - TNG_KSTEP_LO_US) * f);
+        if (S > 1) t += TNG_PUBLISH_US + (S + 1) * elems * 4.0 / TNG_REDUCE_BPUS;
+        if (t < best_t) { best_t = t; best = pl; }
+    }
+    return best;
+}
+
 }  // namespace
 
 extern "C" int alm_gemm_bf16_nt(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long long lda,
@@ -1876,20 +2079,12 @@ extern "C" int alm_gemm_bf16_tn_batched(const void* At, const void* Bt, float* C
     const HybridPlan hy = hybrid_plan(M, N, K, nb);
     if (hy.panels_a > 0) {
         // (a) the panels that fill whole waves of the chip: full K, straight into C -- no partials, no reduce
-        static const int raster_a = [] { const char* e = getenv("ALM_GEMM_HYBRID_RASTER"); return e ? atoi(e) : 2; }();    // A/B switch: 1 = round-robin panels
-        GemmParams pa{(const bf16_t*)At, (const bf16_t*)Bt, C, nullptr, M, N, K, lda, ldb, ldc, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, 0, 0,
-                      (hy.panels_a % 8 == 0 && raster_a == 2) ? 2 : 1, 1, nb, hy.panels_a};
-        rc = launch_gemm<true>(pa, nb, 1, 1, 13, st, true, true);
+        rc = hybrid_panels_launch(At, Bt, C, M, N, K, lda, ldb, ldc, nb1, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, hy, st);
         if (rc) return rc;
         // (b) the last problem's remaining row (column) blocks: an ordinary split-K problem on the sub-matrix, deep enough to fill the chip once
-        const long long zA = (long long)(nb1 - 1) * sA1 + (long long)(nb2 - 1) * sA2, zB = (long long)(nb1 - 1) * sB1 + (long long)(nb2 - 1) * sB2;
-        const long long zC = (long long)(nb1 - 1) * sC1 + (long long)(nb2 - 1) * sC2;
-        const bf16_t* A2 = (const bf16_t*)At + zA + (hy.m_major ? hy.off : 0);
-        const bf16_t* B2 = (const bf16_t*)Bt + zB + (hy.m_major ? 0 : hy.off);
-        float* C2 = C + zC + (hy.m_major ? (long long)hy.off * ldc : hy.off);
-        const int M2 = hy.m_major ? M - hy.off : M, N2 = hy.m_major ? N : N - hy.off;
+        const AlmTnJob t = hybrid_tail(At, Bt, C, M, N, K, lda, ldb, ldc, nb1, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, hy);
         if (!ws) return ALM_ERR_BAD_ARG;
-        rc = splitk_fixed(A2, B2, C2, ws, M2, N2, K, lda, ldb, ldc, hy.slices_b, alpha, accumulate, st);
+        rc = splitk_fixed((const bf16_t*)t.At, (const bf16_t*)t.Bt, t.C, ws, t.M, t.N, K, lda, ldb, ldc, hy.slices_b, alpha, accumulate, st);
         if (rc) return rc;
         ALM_LAUNCH_CHECK();
         return 0;
@@ -1912,6 +2107,89 @@ extern "C" int alm_gemm_bf16_tn_batched(const void* At, const void* Bt, float* C
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid, nb), dim3(256), 0, st, (const float*)ws, nsl, mn, mn * nb, N, C, ldc, sC2, accumulate, nb2, sC1);
     }
     if (rc) return rc;
+    ALM_LAUNCH_CHECK();
+    return 0;
+}
+
+// Step (a) of the hybrid plan above ALONE (the whole-round panels at full K, the same launch: the same bits in those C tiles); what is left -- the same tail
+// (hybrid_tail), or the whole problem when the plan has no whole round -- is handed back as a job for
+// alm_gemm_bf16_tn_grouped instead of being launched.
+extern "C" int alm_gemm_bf16_tn_batched_panels(const void* At, const void* Bt, float* C, int M, int N, int K, long long lda, long long ldb, long long ldc, int nb1,
+                                               int nb2, long long sA1, long long sA2, long long sB1, long long sB2, long long sC1, long long sC2, float alpha,
+                                               int accumulate, AlmTnJob* rest, void* stream) {
+    if (!rest) return ALM_ERR_BAD_ARG;
+    *rest = AlmTnJob{At, Bt, C, M, N, K, nb1, nb2, accumulate, alpha, 0, lda, ldb, ldc, sA1, sA2, sB1, sB2, sC1, sC2};
+    if (M <= 0 || N <= 0 || nb1 <= 0 || nb2 <= 0) { rest->M = 0; return 0; }
+    if (K <= 0 || (lda & 7) || (ldb & 7) || ((sA1 | sA2 | sB1 | sB2) & 7) || ((uintptr_t)At & 15) || ((uintptr_t)Bt & 15)) return ALM_ERR_BAD_ARG;
+    if (view_too_big(K, lda) || view_too_big(K, ldb)) return ALM_ERR_UNSUPPORTED;
+    const HybridPlan hy = hybrid_plan(M, N, K, nb1 * nb2);
+    if (hy.panels_a <= 0) return 0;                                         // no whole round: everything is left
+    const int rc = hybrid_panels_launch(At, Bt, C, M, N, K, lda, ldb, ldc, nb1, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, hy, (hipStream_t)stream);
+    if (rc) return rc;
+    *rest = hybrid_tail(At, Bt, C, M, N, K, lda, ldb, ldc, nb1, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, hy);
+    ALM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int alm_gemm_tn_grouped_plan(const AlmTnJob* jobs, int njobs, int slices, int* plan) {
+    if (tn_jobs_check(jobs, njobs) || slices < 0) return -1;
+    const TnGroupPlan pl = tn_group_plan(jobs, njobs, slices);
+    if (plan) { plan[0] = pl.tiles; plan[1] = pl.S; plan[2] = pl.kps; plan[3] = pl.pieces; plan[4] = pl.blocks; plan[5] = pl.rounds; }
+    return pl.S;
+}
+
+extern "C" int alm_gemm_tn_grouped_ws_floats(const AlmTnJob* jobs, int njobs, int slices) {
+    if (tn_jobs_check(jobs, njobs) || slices < 0) return -1;
+    const TnGroupPlan pl = tn_group_plan(jobs, njobs, slices);
+    return pl.ws_floats > 0x7fffffffLL ? -1 : (int)pl.ws_floats;
+}
+
+extern "C" int alm_gemm_bf16_tn_grouped(const AlmTnJob* jobs, int njobs, float* ws, int slices, void* stream) {
+    int rc = tn_jobs_check(jobs, njobs);
+    if (rc) return rc;
+    if (slices < 0) return ALM_ERR_BAD_ARG;
+    const TnGroupPlan pl = tn_group_plan(jobs, njobs, slices);
+    if (pl.tiles == 0) return 0;
+    const int S = pl.S;
+    if (S > 1 && (!ws || ((uintptr_t)ws & 15) || pl.ws_floats > 0x7fffffffLL)) return ALM_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    TnGroupTable tb;
+    TnGroupPlan geo;
+    tn_group_geometry(jobs, njobs, S, &geo, &tb);
+    TnReduceTable rt;
+    rt.njobs = tb.njobs; rt.S = S; rt.first[0] = 0;
+    long long wso = 0, rmax = 0;
+    int k = 0;
+    for (int i = 0; i < njobs; ++i) {
+        const AlmTnJob& j = jobs[i];
+        if (!tn_job_live(j)) continue;
+        const int nbt = j.nb1 * j.nb2;
+        const long long mn = (long long)j.M * j.N;
+        if (S == 1) {
+            tb.p[k] = GemmParams{(const bf16_t*)j.At, (const bf16_t*)j.Bt, j.C, nullptr, j.M, j.N, j.K, j.lda, j.ldb, j.ldc, j.nb2, j.sA1, j.sA2, j.sB1, j.sB2,
+                                 j.sC1, j.sC2, j.alpha, j.accumulate, 0, 0, 3, 1, nbt};
+        } else {                                                            // partials [S][nbt][M][N] of this job; alpha / accumulate are the reduce's
+            tb.p[k] = GemmParams{(const bf16_t*)j.At, (const bf16_t*)j.Bt, ws + wso, nullptr, j.M, j.N, j.K, j.lda, j.ldb, (long long)j.N, j.nb2, j.sA1, j.sA2,
+                                 j.sB1, j.sB2, mn * j.nb2, mn, 1.0f, 0, pl.kps * BK, mn * nbt, 3, S, nbt};
+            rt.j[k] = TnReduceJob{ws + wso, j.C, mn, mn * nbt, j.ldc, j.sC1, j.sC2, j.N, j.nb2, j.accumulate, j.alpha};
+            wso += ((long long)S * nbt * mn + 3) & ~3LL;
+            rmax = mn > rmax ? mn : rmax;
+        }
+        rt.first[k + 1] = rt.first[k] + nbt;
+        ++k;
+    }
+    constexpr int smem = 163840;
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) return (int)e;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(geo.blocks), dim3(512), smem, st, tb);
+    if (S > 1) {
+        const long long gx = (rmax / 4 + 255) / 256;
+        hipLaunchKernelGGL(tn_grouped_reduce_kernel, dim3((unsigned)(gx < 1 ? 1 : gx > 512 ? 512 : gx), rt.first[k]), dim3(256), 0, st, rt);
+    }
     ALM_LAUNCH_CHECK();
     return 0;
 }

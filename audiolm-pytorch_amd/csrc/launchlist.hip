@@ -70,6 +70,8 @@ const Op OPS[] = {
     ALM_OP(alm_gemm_bf16_nt_splitk),
     ALM_OP(alm_gemm_bf16_tn_splitk),
     ALM_OP(alm_gemm_bf16_tn_batched),
+    ALM_OP(alm_gemm_bf16_tn_batched_panels),      // (its `rest` descriptor is written into the resolved slots of the entry: scratch of this run)
+    ALM_OP(alm_gemm_bf16_tn_grouped),             // (the job table: a host array of 8-byte words whose pointer words the recorder relocates)
     ALM_OP(alm_layernorm_fwd),
     ALM_OP(alm_layernorm_bwd),
     ALM_OP(alm_colsum),

@@ -218,6 +218,19 @@ class Recorder:
                 for j in range(0, len(vals) - 1, 2):
                     self.slots.append(vals[j] | (vals[j + 1] << 32)), self.reloc.append(LITERAL)
                 self.slots[at], self.reloc[at] = here, HOST_INTS
+            elif isinstance(arr._type_, type) and issubclass(arr._type_, ctypes.Structure) and ctypes.sizeof(arr._type_) % 8 == 0:
+                # a table of structs made of 8-byte words (AlmTnJob): its c_void_p words are device pointers placed against the bases like any pointer
+                # argument, every other word is kept as it is; the callee reads (or, for an output descriptor, writes) the RESOLVED slots
+                st, nw = arr._type_, ctypes.sizeof(arr._type_) // 8
+                ptr_words = {getattr(st, f).offset // 8 for f, t_ in st._fields_ if t_ is _P}
+                words = (ctypes.c_ulonglong * (nw * len(arr))).from_buffer_copy(arr)
+                for j, v in enumerate(words):
+                    if j % nw in ptr_words and v:
+                        bid, off = self._classify(int(v), f'{name} host table word {j}')
+                        self.slots.append(off), self.reloc.append(bid)
+                    else:
+                        self.slots.append(int(v)), self.reloc.append(LITERAL)
+                self.slots[at], self.reloc[at] = here, HOST_PTRS
             else:
                 self.fail(f'{name}: host array of {arr._type_.__name__}')
         self.entries.append((op, len(sig), first))
@@ -276,7 +289,7 @@ PLANS = {}
 
 def _switches(core):
     return (core.QKV_GROUP, core.QKV_GROUP_MAX_M, core.ASYNC_KV, core.DEFER_WGRAD, core.DEFER_GROUPS, core.DEFER_GROUP_SIZES, core.DEFER_MAX_BYTES, core.HC_BATCH_FINISH,
-            core.PACK_ALL, core.ASYNC_WGRAD, core.SIDE_STREAMS, ops.NT_WS)
+            core.PACK_ALL, core.ASYNC_WGRAD, core.SIDE_STREAMS, ops.NT_WS, ops.TN_GROUPED)
 
 
 def plan_for(core, x, mask_u8, cfg, need, bias, nflat, defer, dx_scale):

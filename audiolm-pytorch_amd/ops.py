@@ -187,15 +187,24 @@ def gemm_tn_splitk(At, Bt, C, *, alpha=1.0, accumulate=False):
     return _splitk('alm_gemm_bf16_tn_splitk', At, Bt, C, M, N, K, nb, sA, 0, sC, alpha, accumulate)
 
 
-def gemm_tn_batched(At, Bt, C, *, alpha=1.0, accumulate=False):
+def gemm_tn_batched(At, Bt, C, *, alpha=1.0, accumulate=False, leftovers=None):
     """fp32 C[n1, n2, M, N] (+)= alpha * At[n1, n2, K, M]^T @ Bt[n1, n2, K, N]: 4-D strided views (last dim contiguous; a size-1 / stride-0 leading dim of Bt
-    broadcasts), e.g. every layer's gradient of one weight kind from stacked activation buffers in ONE launch."""
+    broadcasts), e.g. every layer's gradient of one weight kind from stacked activation buffers in ONE launch.
+    leftovers: a list -> only the panels that fill whole rounds of the chip are launched (alm_gemm_bf16_tn_batched_panels) and the job that is left (the
+    hybrid plan's tail, or the whole problem) is appended to it: C is complete only after gemm_tn_grouped(leftovers)."""
     _chk(At, BF16), _chk(Bt, BF16), _chk(C, F32)
     assert At.dim() == 4 and Bt.dim() == 4 and C.dim() == 4 and At.stride(-1) == 1 and Bt.stride(-1) == 1 and C.stride(-1) == 1
     n1, n2, K, M = At.shape
     N = Bt.shape[-1]
     assert Bt.shape[-2] == K and tuple(C.shape) == (n1, n2, M, N), (At.shape, Bt.shape, C.shape)
     sb = [Bt.stride(0) if Bt.shape[0] != 1 else 0, Bt.stride(1) if Bt.shape[1] != 1 else 0]
+    if leftovers is not None:
+        rest = (_lib.AlmTnJob * 1)()
+        _lib.call('alm_gemm_bf16_tn_batched_panels', At.data_ptr(), Bt.data_ptr(), C.data_ptr(), M, N, K, At.stride(-2), Bt.stride(-2), C.stride(-2), n1, n2,
+                  At.stride(0), At.stride(1), sb[0], sb[1], C.stride(0), C.stride(1), float(alpha), int(accumulate), rest, _st())
+        if rest[0].M > 0:
+            leftovers.append((rest, At, Bt, C))          # (the tensors: kept alive until the grouped launch is issued)
+        return C
     nws = _lib.query('alm_gemm_splitk_ws_floats', M, N, K, n1 * n2)
     if nws < 0:
         raise _lib.AlmError('split-K workspace exceeds 2^31 floats')
@@ -203,6 +212,54 @@ def gemm_tn_batched(At, Bt, C, *, alpha=1.0, accumulate=False):
     _lib.call('alm_gemm_bf16_tn_batched', At.data_ptr(), Bt.data_ptr(), C.data_ptr(), _p(ws), M, N, K, At.stride(-2), Bt.stride(-2), C.stride(-2), n1, n2,
               At.stride(0), At.stride(1), sb[0], sb[1], C.stride(0), C.stride(1), float(alpha), int(accumulate), _st())
     return C
+
+
+TN_GROUP_MAX = 8
+# The parts of the stack's five batched weight-gradient launches that do not fill whole rounds of the chip are finished by ONE grouped launch (core.stack_backward,
+# single group, no gradient hook).  ALM_TN_GROUPED=0: today's per-kind calls (A/B switch; interleaved on one box: 11.72 -> 11.58 ms/step, docs/LABBOOK.md round 7)
+TN_GROUPED = os.environ.get('ALM_TN_GROUPED', '1') != '0'
+
+
+def _tn_jobs(leftovers):
+    arr = (_lib.AlmTnJob * len(leftovers))()
+    for i, lo in enumerate(leftovers):
+        ctypes.memmove(ctypes.byref(arr, i * ctypes.sizeof(_lib.AlmTnJob)), lo[0], ctypes.sizeof(_lib.AlmTnJob))
+    return arr
+
+
+def gemm_tn_grouped_plan(leftovers, slices=0):
+    """(tiles, slices, K-steps per slice, pieces, workgroups, rounds) of gemm_tn_grouped(leftovers, slices) -- no launch"""
+    plan = (ctypes.c_int * 6)()
+    if _lib.query('alm_gemm_tn_grouped_plan', _tn_jobs(leftovers), len(leftovers), int(slices), ctypes.cast(plan, ctypes.c_void_p)) < 0:
+        raise _lib.AlmError('alm_gemm_tn_grouped_plan: bad job table')
+    return tuple(plan)
+
+
+def gemm_tn_grouped(leftovers, slices=0):
+    """finishes the C of every gemm_tn_batched(..., leftovers=leftovers) call: the jobs' 256 x 256 tiles, cut into ONE number of K slices, in one launch and
+    one fixed-order reduce (alm_gemm_bf16_tn_grouped; at most 8 jobs per launch, all of one K).  slices: 0 = the library's cost model."""
+    for g0 in range(0, len(leftovers), TN_GROUP_MAX):
+        arr = _tn_jobs(leftovers[g0:g0 + TN_GROUP_MAX])
+        nws = _lib.query('alm_gemm_tn_grouped_ws_floats', arr, len(arr), int(slices))
+        if nws < 0:
+            raise _lib.AlmError('alm_gemm_tn_grouped: bad job table, or its split-K workspace exceeds 2^31 floats')
+        dev = next(lo[1].device for lo in leftovers[g0:g0 + TN_GROUP_MAX])
+        ws = _new(nws, dtype=F32, device=dev) if nws > 0 else None
+        _lib.call('alm_gemm_bf16_tn_grouped', arr, len(arr), _p(ws), int(slices), _st())
+
+
+def tn_job(At, Bt, C, *, alpha=1.0, accumulate=False):
+    """a whole gemm_tn_batched problem as a job of gemm_tn_grouped (nothing launched)"""
+    _chk(At, BF16), _chk(Bt, BF16), _chk(C, F32)
+    assert At.dim() == 4 and Bt.dim() == 4 and C.dim() == 4 and At.stride(-1) == 1 and Bt.stride(-1) == 1 and C.stride(-1) == 1
+    n1, n2, K, M = At.shape
+    N = Bt.shape[-1]
+    assert Bt.shape[-2] == K and tuple(C.shape) == (n1, n2, M, N), (At.shape, Bt.shape, C.shape)
+    sb = [Bt.stride(0) if Bt.shape[0] != 1 else 0, Bt.stride(1) if Bt.shape[1] != 1 else 0]
+    job = (_lib.AlmTnJob * 1)()
+    job[0] = _lib.AlmTnJob(At.data_ptr(), Bt.data_ptr(), C.data_ptr(), M, N, K, n1, n2, int(accumulate), float(alpha), 0, At.stride(-2), Bt.stride(-2),
+                           C.stride(-2), At.stride(0), At.stride(1), sb[0], sb[1], C.stride(0), C.stride(1))
+    return (job, At, Bt, C)
 
 
 def gemm_nt_tile(A, B, C, tile, *, bias=None, alpha=1.0, accumulate=False):

@@ -84,6 +84,28 @@ int alm_gemm_bf16_tn_splitk(const void* At, const void* Bt, float* C, float* ws,
 int alm_gemm_bf16_tn_batched(const void* At, const void* Bt, float* C, float* ws, int M, int N, int K, long long lda, long long ldb, long long ldc,
                              int nb1, int nb2, long long sA1, long long sA2, long long sB1, long long sB2, long long sC1, long long sC2, float alpha,
                              int accumulate, void* stream);
+/* Grouped leftovers of the batched weight gradients.  The parts of the _tn_batched calls that do not fill whole rounds of the chip's 256 CUs (the tails of
+ * the hybrid plan, the weight kinds with few tiles) are independent and contract over the same K: ONE launch cuts the 256 x 256 tiles of up to 8 jobs into
+ * uniform K slices that fill whole rounds, ONE table-driven reduce sums the slices in slice order (a fixed function of the inputs: no atomics).
+ * A job is one two-level batched _tn_ problem (every field as in alm_gemm_bf16_tn_batched; 16 eight-byte words, no padding). */
+typedef struct {
+    const void* At; const void* Bt; float* C;
+    int M, N, K, nb1, nb2, accumulate; float alpha; int reserved;
+    long long lda, ldb, ldc, sA1, sA2, sB1, sB2, sC1, sC2;
+} AlmTnJob;
+/*   _batched_panels: step (a) of alm_gemm_bf16_tn_batched's hybrid plan alone -- the panels that fill whole rounds, at full K, straight into C (the same
+ *     kernel, raster and arithmetic: those C tiles are bitwise the ones alm_gemm_bf16_tn_batched writes) -- and `rest` = what is left as a job: the tail's
+ *     sub-matrix of the last problem, or the whole problem when the plan has no whole round (then nothing is launched).  rest->M == 0: nothing left.
+ *   _grouped: the jobs (all of one K) in one launch + one reduce.  slices: 0 = the cost model's choice, > 0 = that many (lowered to what K allows);
+ *     1 = no partials, no reduce (ws may be NULL).  ws: alm_gemm_tn_grouped_ws_floats(jobs, njobs, slices) floats.
+ *   _grouped_plan (no launch): plan[0] = 256 x 256 tiles of all jobs, plan[1] = slices S, plan[2] = K-steps (of 64) per slice, plan[3] = pieces
+ *     (tiles x S), plan[4] = workgroups launched, plan[5] = rounds of the busiest XCD's 32 CUs; plan: int[6] | NULL; returns S (< 0: bad jobs). */
+int alm_gemm_bf16_tn_batched_panels(const void* At, const void* Bt, float* C, int M, int N, int K, long long lda, long long ldb, long long ldc,
+                                    int nb1, int nb2, long long sA1, long long sA2, long long sB1, long long sB2, long long sC1, long long sC2, float alpha,
+                                    int accumulate, AlmTnJob* rest, void* stream);
+int alm_gemm_bf16_tn_grouped(const AlmTnJob* jobs, int njobs, float* ws, int slices, void* stream);
+int alm_gemm_tn_grouped_plan(const AlmTnJob* jobs, int njobs, int slices, int* plan);
+int alm_gemm_tn_grouped_ws_floats(const AlmTnJob* jobs, int njobs, int slices);
 /* dst[c][r] = src[r][c]; columns [rows, rows_pad) of dst are zero-filled (K-padding of a transposed GEMM operand). */
 int alm_transpose_bf16(const void* src, void* dst, int rows, int cols, long long ld_src, long long ld_dst, int rows_pad, void* stream);
 /* nb matrices (element strides bs_src / bs_dst) in ONE launch: the per-sequence key / value sets of a conditioning context (xattn.py). */
