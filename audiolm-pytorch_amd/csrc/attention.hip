@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "../../include/audiolm_hip.h"
 
 namespace {
@@ -1413,22 +1414,10 @@ static int attn_bwd_impl(const void* q, long long ldq, const void* k, long long 
     const int nh = dkv_heads_per_block(B, N, H);
     p.HG = (H + nh - 1) / nh;
     p.dkv_split = dkv_split(B, N, H, nh);
-    auto launch_dkv = [&](auto kern, int threads, int lds) -> hipError_t {
-        // the LDS attribute is set once per KERNEL: the eight instantiations below are eight function-pointer VALUES of one type (one operator() of this
-        // lambda, one static): keyed on the value (ADVICE r5 found a per-type flag shared by four kernels in the grouped GEMM launcher)
-        static const void* done[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        const void* fn = reinterpret_cast<const void*>(kern);
-        bool seen = false;
-        for (int i = 0; i < 8; ++i) seen = seen || done[i] == fn;
-        if (!seen) {
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return e;
-            for (int i = 0; i < 8; ++i) if (done[i] == nullptr) { done[i] = fn; break; }
-        }
-        hipLaunchKernelGGL(kern, dim3(nqb * p.HG * p.dkv_split * B), dim3(threads), lds, st, p);
-        return hipSuccess;
+    auto launch_dkv = [&](auto kern, int threads, int lds) -> int {
+        return alm_launch_lds(kern, dim3(nqb * p.HG * p.dkv_split * B), dim3(threads), lds, st, p);
     };
-    hipError_t le;
+    int le;
     if (nh == 2) {
         constexpr int LDS2 = 2 * 2 * 16384 + 2 * 2 * 512;
         if (drop) le = p.tbl ? launch_dkv(mqa_bwd_dkv_kernel<true, true, 2>, 256, LDS2) : launch_dkv(mqa_bwd_dkv_kernel<false, true, 2>, 256, LDS2);
@@ -1438,7 +1427,7 @@ static int attn_bwd_impl(const void* q, long long ldq, const void* k, long long 
         if (drop) le = p.tbl ? launch_dkv(mqa_bwd_dkv_kernel<true, true, 4>, 512, LDS4) : launch_dkv(mqa_bwd_dkv_kernel<false, true, 4>, 512, LDS4);
         else le = p.tbl ? launch_dkv(mqa_bwd_dkv_kernel<true, false, 4>, 512, LDS4) : launch_dkv(mqa_bwd_dkv_kernel<false, false, 4>, 512, LDS4);
     }
-    if (le != hipSuccess) return (int)le;
+    if (le) return le;
     ALM_LAUNCH_CHECK();
     return 0;
 }

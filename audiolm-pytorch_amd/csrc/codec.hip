@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "conv1d.hpp"
 #include "../../include/audiolm_hip.h"
 
@@ -646,13 +647,8 @@ extern "C" int alm_rvq_encode(const float* x, long long ldx, const float* E, con
     const int nw = nw_env == 4 || nw_env == 8 ? nw_env : (cost8 < cost4 ? 8 : 4);
     const size_t smem = (size_t)(32 * (alm_rvq_padded_dim(d) + 4) + 32 + 32 * nw) * sizeof(float) + (32 * nw + 32) * sizeof(int);
     if (smem > 160 * 1024) return ALM_ERR_UNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rvq_encode_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(rvq_encode_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    const int rc = alm_lds_limit(nw == 4 ? reinterpret_cast<const void*>(rvq_encode_kernel<4>) : reinterpret_cast<const void*>(rvq_encode_kernel<8>), 160 * 1024);
+    if (rc) return rc;
     RvqArgs a{x, ldx, E, Et, e2, idx, ldi, quant, ldq, T, d, C, alm_rvq_padded_codes(C), Q};
     if (nw == 8) hipLaunchKernelGGL(rvq_encode_kernel<8>, dim3((unsigned)tiles), dim3(512), smem, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(rvq_encode_kernel<4>, dim3((unsigned)tiles), dim3(256), smem, (hipStream_t)stream, a);

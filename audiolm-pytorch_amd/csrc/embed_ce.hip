@@ -6,6 +6,7 @@
 //     (reference F.cross_entropy(ignore_index = -1), audiolm_pytorch.py:1561-1565, :1839-1849, :2122-2132)
 //   * value-residual mixing v <- (v + v_layer0) / 2 (:357-358) and the matching gradient fan-in.
 #include "common.hpp"
+#include "launch.hpp"
 #include "../../include/audiolm_hip.h"
 
 namespace {
@@ -934,13 +935,8 @@ extern "C" int alm_embed_scatter_owned(float* const* grad_tables, const int* tab
                            (int)(pl.int_fl / 4));
     if ((t.nsmall > 0 || pl.hot) && t.nchunks > 0) {
         const size_t smem = 2 * OWN_CH * sizeof(int) + (size_t)t.nsmall * 256 * sizeof(float4);       // <= 256 B + 32 x 4 KB
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(embed_scatter_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)(2 * OWN_CH * sizeof(int) + SMALL_ROWS * 256 * sizeof(float4)));
-            if (e != hipSuccess) return (int)e;
-            attr_done = true;
-        }
+        const int rc = alm_lds_limit(reinterpret_cast<const void*>(embed_scatter_small_kernel), (int)(2 * OWN_CH * sizeof(int) + SMALL_ROWS * 256 * sizeof(float4)));
+        if (rc) return rc;
         hipLaunchKernelGGL(embed_scatter_small_kernel, dim3((unsigned)t.nchunks, (unsigned)((D + 1023) / 1024)), dim3(256), smem, (hipStream_t)stream, t, src_a,
                            src_b, dout, alpha, rows, D, ws, iw);
     }

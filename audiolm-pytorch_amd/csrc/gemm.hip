@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "../../include/audiolm_hip.h"
 
 // Cache policy of the operand DMA (`buffer_load ... lds` aux immediate: 1 = sc0, 2 = nt, 16 = sc1).  0 in the product build; scripts/build_variant.sh
@@ -1395,99 +1396,33 @@ __global__ __launch_bounds__(256) void pack_weights_multi3_kernel(PackJobs3 pj) 
     }
 }
 
-// ---- launch plumbing ---------------------------------------------------------------------------------------------------------
+// ---- launch plumbing (launch.hpp: per-kernel, per-device dynamic-LDS limit + the raster grid) ------------------------------------
 template <int BM, int BN, int WM, int WN, bool TNMODE, bool OUT_F32>
 int launch_cfg(const GemmParams& p, int ny, int nz, hipStream_t st) {
-    constexpr int smem = 2 * (BM + BN) * BK * 2;
-    static bool attr_done = false;                 // idempotent; a benign race sets the same value twice
-    auto kfn = gemm_kernel<BM, BN, WM, WN, TNMODE, OUT_F32>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
-    if (p.raster >= 1) {
-        const int tmaj = tiles_m >= tiles_n ? tiles_m : tiles_n, Q = tiles_m >= tiles_n ? tiles_n : tiles_m;
-        const int PL = ((p.plimit > 0 ? p.plimit : tmaj * ny) + 7) / 8;
-        hipLaunchKernelGGL(kfn, dim3(8 * PL * Q * nz), dim3(WM * WN * 64), smem, st, p);
-        return 0;
-    }
-    hipLaunchKernelGGL(kfn, dim3(tiles_m * tiles_n, ny, nz), dim3(WM * WN * 64), smem, st, p);
-    return 0;
+    return alm_launch_raster<BM, BN, WM * WN * 64, 2 * (BM + BN) * BK * 2>(gemm_kernel<BM, BN, WM, WN, TNMODE, OUT_F32>, p, p.raster >= 1, p.plimit, ny, nz, st);
 }
 
 template <bool OUT_F32>
 int launch_ring(const GemmParams& p, int ny, int nz, hipStream_t st) {          // tile 16: 128 x 128, 4 waves, 4-stage DMA ring (128 KB of LDS, NT, raster 0)
-    constexpr int smem = 4 * (128 + 128) * BK * 2;
-    static bool attr_done = false;
-    auto kfn = gemm_ring_kernel<128, 128, 2, 2, false, OUT_F32, 4>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(((p.M + 127) / 128) * ((p.N + 127) / 128), ny, nz), dim3(256), smem, st, p);
-    return 0;
+    return alm_launch_lds(gemm_ring_kernel<128, 128, 2, 2, false, OUT_F32, 4>, dim3(((p.M + 127) / 128) * ((p.N + 127) / 128), ny, nz), dim3(256),
+                          4 * (128 + 128) * BK * 2, st, p);
 }
 
 template <bool TNMODE, bool OUT_F32>
 int launch_stag(const GemmParams& p, int ny, int nz, hipStream_t st) {
-    constexpr int smem = 163840;
-    static bool attr_done = false;
-    auto kfn = gemm_stag_kernel<TNMODE, OUT_F32>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    const int tiles_m = (p.M + 255) / 256, tiles_n = (p.N + 255) / 256;
-    if (p.raster >= 1) {
-        const int tmaj = tiles_m >= tiles_n ? tiles_m : tiles_n, Q = tiles_m >= tiles_n ? tiles_n : tiles_m;
-        const int PL = ((p.plimit > 0 ? p.plimit : tmaj * ny) + 7) / 8;
-        hipLaunchKernelGGL(kfn, dim3(8 * PL * Q * nz), dim3(512), smem, st, p);
-        return 0;
-    }
-    hipLaunchKernelGGL(kfn, dim3(tiles_m * tiles_n, ny, nz), dim3(512), smem, st, p);
-    return 0;
+    return alm_launch_raster<256, 256, 512, 163840>(gemm_stag_kernel<TNMODE, OUT_F32>, p, p.raster >= 1, p.plimit, ny, nz, st);
 }
-
 
 // in-launch split-K launch of the staggered NT tile: p.inl_ws / p.inl_cnt / p.inl_slices / p.ksplit set by the caller (nt_launch_ws); raster 0
 template <bool OUT_F32>
 int launch_stag_inl(const GemmParams& p, int ny, hipStream_t st) {
-    constexpr int smem = 163840;
-    static bool attr_done = false;
-    auto kfn = gemm_stag_inl_kernel<OUT_F32>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
     const int tiles_m = (p.M + 255) / 256, tiles_n = (p.N + 255) / 256;
-    hipLaunchKernelGGL(kfn, dim3(tiles_m * tiles_n, ny, p.inl_slices), dim3(512), smem, st, p);
-    return 0;
+    return alm_launch_lds(gemm_stag_inl_kernel<OUT_F32>, dim3(tiles_m * tiles_n, ny, p.inl_slices), dim3(512), 163840, st, p);
 }
 
 template <bool TNMODE, bool OUT_F32>
 int launch_w4(const GemmParams& p, int ny, int nz, hipStream_t st) {
-    constexpr int smem = 131072;
-    static bool attr_done = false;
-    auto kfn = gemm_w4_kernel<TNMODE, OUT_F32>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    const int tiles_m = (p.M + 255) / 256, tiles_n = (p.N + 255) / 256;
-    if (p.raster >= 1) {
-        const int tmaj = tiles_m >= tiles_n ? tiles_m : tiles_n, Q = tiles_m >= tiles_n ? tiles_n : tiles_m;
-        const int PL = ((p.plimit > 0 ? p.plimit : tmaj * ny) + 7) / 8;
-        hipLaunchKernelGGL(kfn, dim3(8 * PL * Q * nz), dim3(256), smem, st, p);
-        return 0;
-    }
-    hipLaunchKernelGGL(kfn, dim3(tiles_m * tiles_n, ny, nz), dim3(256), smem, st, p);
-    return 0;
+    return alm_launch_raster<256, 256, 256, 131072>(gemm_w4_kernel<TNMODE, OUT_F32>, p, p.raster >= 1, p.plimit, ny, nz, st);
 }
 
 // Tile ids (alm_gemm_bf16_nt_tile): 1 = 128 x 128 (4 waves, two workgroups per CU), 2 = 256 x 256 lock-step (8 waves), 13 = 256 x 256 with
@@ -1938,22 +1873,11 @@ extern "C" int alm_gemm_bf16_nt_group2(const void* A0, const void* B0, void* C0,
     GemmParams p1{(const bf16_t*)A1, (const bf16_t*)B1, C1, nullptr, M1, N1, K1, lda1, ldb1, ldc1, 1, 0, 0, 0, 0, 0, 0, 1.f, 0, 0, 0, 0, 1};
     p0.group_m = pick_group(p0, t0);
     p1.group_m = pick_group(p1, t1);
-    // ONE dynamic-LDS attribute flag PER KERNEL (`which`): the four kernels decay to one function-pointer type, so a generic lambda with a local static would
-    // share a single flag between them and only the first variant launched in a process would get its attribute (round-5 advisor finding)
-    auto launch = [&](auto kfn, int which, int threads, int smem) -> int {
-        static bool attr_done[4] = {false, false, false, false};
-        if (!attr_done[which]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return (int)e;
-            attr_done[which] = true;
-        }
-        hipLaunchKernelGGL(kfn, dim3(tiles0 + tiles1), dim3(threads), smem, st, p0, p1, tiles0);
-        return 0;
-    };
+    auto launch = [&](auto kfn, int threads, int smem) -> int { return alm_launch_lds(kfn, dim3(tiles0 + tiles1), dim3(threads), smem, st, p0, p1, tiles0); };
     int rc;
-    if (t0 == 1) rc = out_f32 ? launch(gemm_group2_kernel<128, 128, 2, 2, false, true>, 0, 256, 2 * (128 + 128) * BK * 2)
-                              : launch(gemm_group2_kernel<128, 128, 2, 2, false, false>, 1, 256, 2 * (128 + 128) * BK * 2);
-    else rc = out_f32 ? launch(gemm_stag_group2_kernel<false, true>, 2, 512, 163840) : launch(gemm_stag_group2_kernel<false, false>, 3, 512, 163840);
+    if (t0 == 1) rc = out_f32 ? launch(gemm_group2_kernel<128, 128, 2, 2, false, true>, 256, 2 * (128 + 128) * BK * 2)
+                              : launch(gemm_group2_kernel<128, 128, 2, 2, false, false>, 256, 2 * (128 + 128) * BK * 2);
+    else rc = out_f32 ? launch(gemm_stag_group2_kernel<false, true>, 512, 163840) : launch(gemm_stag_group2_kernel<false, false>, 512, 163840);
     if (rc) return rc;
     ALM_LAUNCH_CHECK();
     return 0;
@@ -2178,14 +2102,8 @@ extern "C" int alm_gemm_bf16_tn_grouped(const AlmTnJob* jobs, int njobs, float* 
         rt.first[k + 1] = rt.first[k] + nbt;
         ++k;
     }
-    constexpr int smem = 163840;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(geo.blocks), dim3(512), smem, st, tb);
+    rc = alm_launch_lds(gemm_tn_grouped_kernel, dim3(geo.blocks), dim3(512), 163840, st, tb);
+    if (rc) return rc;
     if (S > 1) {
         const long long gx = (rmax / 4 + 255) / 256;
         hipLaunchKernelGGL(tn_grouped_reduce_kernel, dim3((unsigned)(gx < 1 ? 1 : gx > 512 ? 512 : gx), rt.first[k]), dim3(256), 0, st, rt);

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "../common.hpp"
+#include "../launch.hpp"
 #include "../../../include/audiolm_hip.h"      // error codes only
 #include "gemm_lab.h"
 
@@ -1330,23 +1331,7 @@ __global__ __launch_bounds__(256) void pack_weights_multi_kernel(PackJobs pj) {
 // ---- launch plumbing ---------------------------------------------------------------------------------------------------------
 template <int BM, int BN, int WM, int WN, bool TNMODE, bool OUT_F32, int STAGES = 2, bool PIPE = false>
 int launch_cfg(const GemmParams& p, int ny, int nz, hipStream_t st) {
-    constexpr int smem = STAGES * (BM + BN) * BK * 2;
-    static bool attr_done = false;                 // idempotent; a benign race sets the same value twice
-    auto kfn = gemm_kernel<BM, BN, WM, WN, TNMODE, OUT_F32, STAGES, PIPE>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
-    if (p.raster == 1) {
-        const int tmaj = tiles_m >= tiles_n ? tiles_m : tiles_n, Q = tiles_m >= tiles_n ? tiles_n : tiles_m;
-        const int PL = (tmaj * ny + 7) / 8;
-        hipLaunchKernelGGL(kfn, dim3(8 * PL * Q * nz), dim3(WM * WN * 64), smem, st, p);
-        return 0;
-    }
-    hipLaunchKernelGGL(kfn, dim3(tiles_m * tiles_n, ny, nz), dim3(WM * WN * 64), smem, st, p);
-    return 0;
+    return alm_launch_raster<BM, BN, WM * WN * 64, STAGES * (BM + BN) * BK * 2>(gemm_kernel<BM, BN, WM, WN, TNMODE, OUT_F32, STAGES, PIPE>, p, p.raster == 1, 0, ny, nz, st);
 }
 
 // tile: 0 = auto, 1 = 128x128 (4 waves, 2 blocks / CU), 2 = 256x256 (8 waves, 1 block / CU), 3 = 256x128 with a 3-stage DMA ring (8 waves)
@@ -1359,38 +1344,13 @@ int pick_tile(int M, int N, int ny, int tile) {
 
 template <bool TNMODE, bool OUT_F32>
 int launch_stag(const GemmParams& p, int ny, int nz, hipStream_t st) {
-    constexpr int smem = 163840;
-    static bool attr_done = false;
-    auto kfn = gemm_stag_kernel<TNMODE, OUT_F32>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    const int tiles_m = (p.M + 255) / 256, tiles_n = (p.N + 255) / 256;
-    if (p.raster == 1) {
-        const int tmaj = tiles_m >= tiles_n ? tiles_m : tiles_n, Q = tiles_m >= tiles_n ? tiles_n : tiles_m;
-        const int PL = (tmaj * ny + 7) / 8;
-        hipLaunchKernelGGL(kfn, dim3(8 * PL * Q * nz), dim3(512), smem, st, p);
-        return 0;
-    }
-    hipLaunchKernelGGL(kfn, dim3(tiles_m * tiles_n, ny, nz), dim3(512), smem, st, p);
-    return 0;
+    return alm_launch_raster<256, 256, 512, 163840>(gemm_stag_kernel<TNMODE, OUT_F32>, p, p.raster == 1, 0, ny, nz, st);
 }
 
 template <bool OUT_F32>
 int launch_persist(const GemmParams& p, int ny, hipStream_t st) {
-    constexpr int smem = 2 * (256 + 256) * BK * 2;
-    static bool attr_done = false;
-    auto kfn = gemm_nt_persist_kernel<OUT_F32>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
     const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-    hipLaunchKernelGGL(kfn, dim3(tiles < 256 ? tiles : 256, ny), dim3(512), smem, st, p);
-    return 0;
+    return alm_launch_lds(gemm_nt_persist_kernel<OUT_F32>, dim3(tiles < 256 ? tiles : 256, ny), dim3(512), 2 * (256 + 256) * BK * 2, st, p);
 }
 
 template <bool OUT_F32, bool PIPE>
@@ -1403,17 +1363,8 @@ int launch_bdirect(const GemmParams& p, int ny, hipStream_t st) {
 
 template <bool OUT_F32, int NST, int BNX, int WNX>
 int launch_ring(const GemmParams& p, int ny, hipStream_t st) {
-    constexpr int smem = NST * (256 + BNX) * 32 * 2;
-    static bool attr_done = false;
-    void (*kfn)(GemmParams) = &gemm_nt_ring_kernel<OUT_F32, NST, BNX, WNX>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
     const int tiles = ((p.M + 255) / 256) * ((p.N + BNX - 1) / BNX);
-    hipLaunchKernelGGL((gemm_nt_ring_kernel<OUT_F32, NST, BNX, WNX>), dim3(tiles, ny), dim3(2 * WNX * 64), smem, st, p);
-    return 0;
+    return alm_launch_lds(gemm_nt_ring_kernel<OUT_F32, NST, BNX, WNX>, dim3(tiles, ny), dim3(2 * WNX * 64), NST * (256 + BNX) * 32 * 2, st, p);
 }
 
 template <bool TNMODE>
@@ -1672,15 +1623,9 @@ static int splitk_common(bool tn, const void* A, const void* B, float* C, float*
         const StreamPlan* sp = get_stream_plan(M, N, K, nb);
         if (!sp) return ALM_ERR_UNSUPPORTED;
         GemmParams p{(const bf16_t*)A, (const bf16_t*)B, ws, nullptr, M, N, K, lda, ldb, 256, nb, 0, sA, 0, sB, 0, 0, alpha, 0, 0, 0, 0, 1, sp->d_units};
-        static bool attr_done[2] = {false, false};
         auto kfn = tn ? gemm_kernel<256, 256, 2, 4, true, true> : gemm_kernel<256, 256, 2, 4, false, true>;
-        constexpr int smem = 2 * (256 + 256) * BK * 2;
-        if (!attr_done[tn]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return (int)e;
-            attr_done[tn] = true;
-        }
-        hipLaunchKernelGGL(kfn, dim3(sp->nunits), dim3(512), smem, st, p);
+        const int rc = alm_launch_lds(kfn, dim3(sp->nunits), dim3(512), 2 * (256 + 256) * BK * 2, st, p);
+        if (rc) return rc;
         const int tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256;
         hipLaunchKernelGGL((stream_reduce_kernel<256, 256>), dim3(tiles_m * tiles_n * nb, 16), dim3(256), 0, st, (const float*)ws, sp->d_tile_first, C, ldc,
                            sC, M, N, tiles_m, tiles_n, accumulate);

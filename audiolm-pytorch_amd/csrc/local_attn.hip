@@ -11,6 +11,7 @@
 // a plain fp32 VALU kernel -- one thread per query, keys / values of the window pair in LDS transposed to [feature][slot] (conflict-free:
 // the lanes of a wave read consecutive slots) -- not an MFMA tiling.
 #include "common.hpp"
+#include "launch.hpp"
 #include "../../include/audiolm_hip.h"
 
 namespace {
@@ -144,13 +145,9 @@ int launch_local(const float* qkv, const float* q_scale, const float* k_scale, c
                  const float* gates, float* out, int B, int H, int T, int W, float scale, hipStream_t st) {
     const int smem = 2 * DH * 2 * W * (int)sizeof(float);
     if (smem > 160 * 1024) return ALM_ERR_UNSUPPORTED;
-    static bool attr_done = false;
     auto kfn = local_attn_kernel<DH>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    const int rc = alm_lds_limit(reinterpret_cast<const void*>(kfn), 160 * 1024);
+    if (rc) return rc;
     hipLaunchKernelGGL(kfn, dim3((T + W - 1) / W, H, B), dim3(W), smem, st, qkv, q_scale, k_scale, cos_t, sin_t, xpos_t, gates, out, H, T, W, scale);
     return 0;
 }

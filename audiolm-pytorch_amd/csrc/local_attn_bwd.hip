@@ -14,6 +14,7 @@
 //     dgamma / dbeta one workgroup per channel (thread-strided partial sums + a fixed LDS tree).
 //   * GEGLU backward with the forward's erf GELU and its exact derivative.
 #include "common.hpp"
+#include "launch.hpp"
 #include "../../include/audiolm_hip.h"
 
 namespace {
@@ -338,16 +339,11 @@ int launch_bwd(const float* qkv, const float* q_scale, const float* k_scale, con
     if (smem_q > LDS_LIMIT) return ALM_ERR_UNSUPPORTED;
     const bool lds_stats = smem_q + 4 * W * (int)sizeof(float) <= LDS_LIMIT;
     const int smem_k = lds_stats ? smem_q + 4 * W * (int)sizeof(float) : smem_q;
-    static bool attr_done = false;
     auto kq = local_attn_bwd_dq_kernel<DH>;
     auto kk = lds_stats ? local_attn_bwd_dkv_kernel<DH, true> : local_attn_bwd_dkv_kernel<DH, false>;
-    if (!attr_done) {
-        for (const void* f : {reinterpret_cast<const void*>(kq), reinterpret_cast<const void*>(local_attn_bwd_dkv_kernel<DH, true>),
-                              reinterpret_cast<const void*>(local_attn_bwd_dkv_kernel<DH, false>)}) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
-            if (e != hipSuccess) return (int)e;
-        }
-        attr_done = true;
+    for (const void* f : {reinterpret_cast<const void*>(kq), reinterpret_cast<const void*>(kk)}) {
+        const int rc = alm_lds_limit(f, LDS_LIMIT);
+        if (rc) return rc;
     }
     const int NW = (T + W - 1) / W;
     const long long BHT = (long long)B * H * T, P = (long long)B * H * NW;

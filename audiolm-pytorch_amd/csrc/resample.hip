@@ -15,6 +15,7 @@
 // ds_read_b128) when it fits RS_TABLE_LDS_BUDGET, else read from global memory, where it stays L2-resident.  The outputs go through LDS
 // (aliasing the input window) and leave as J rows of PT contiguous floats: coalesced plain vector stores.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -132,13 +133,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(RsArgs a) {
 
 template <int PR, bool TLDS, bool ADJ>
 int rs_launch(const RsArgs& a, unsigned gx, unsigned gy, size_t lds, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(resample_kernel<PR, TLDS, ADJ>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)RS_LDS_MAX);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    const int rc = alm_lds_limit(reinterpret_cast<const void*>(resample_kernel<PR, TLDS, ADJ>), (int)RS_LDS_MAX);
+    if (rc) return rc;
     hipLaunchKernelGGL((resample_kernel<PR, TLDS, ADJ>), dim3(gx, gy), dim3(RS_THREADS), lds, st, a);
     ALM_LAUNCH_CHECK();
     return 0;

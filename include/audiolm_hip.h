@@ -9,7 +9,9 @@
  *   - plain C types only; every pointer is a DEVICE pointer owned by the caller (PyTorch allocator), incl. workspaces
  *   - bf16 tensors are raw uint16 bit patterns (void*); fp32 statistics / master weights / gradients are float*
  *   - `ld*` = leading dimension (row stride) in ELEMENTS; row-major everywhere
- *   - kernels are stateless, re-entrant, asynchronous on `stream` (a hipStream_t passed as void*); callable from any thread
+ *   - kernels are stateless, re-entrant, asynchronous on `stream` (a hipStream_t passed as void*); callable from any thread.
+ *     The launchers' only process state is the dynamic-LDS limit table (csrc/launch.hpp): which (kernel, device) pairs already had
+ *     hipFuncAttributeMaxDynamicSharedMemorySize raised, guarded by a mutex -- a second GPU gets its own entries
  *   - return 0 on success, a hipError_t value (> 0) or ALM_ERR_* (>= 10001) otherwise; nothing is printed
  */
 #pragma once

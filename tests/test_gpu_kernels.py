@@ -74,6 +74,23 @@ def test_gemm_nt_tile_configs(ops, M, N, K, tile):
         assert bool(torch.isnan(C[M:]).all()) and bool(torch.isnan(C[:, N:]).all()), 'GEMM wrote outside its tile'
 
 
+def test_gemm_nt_big_lds_tile_on_a_second_device(ops):
+    """the staggered 256 x 256 tile (13) needs 160 KB of dynamic LDS: the limit is raised per (kernel, device) (csrc/launch.hpp), so the same process can
+    launch it on cuda:0 and then on cuda:1.  Same reference and tolerances as test_gemm_nt_tile_configs; the bookkeeping itself: tests/test_launch_table.py."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip('needs two GPUs: the dynamic-LDS limit is a per-device attribute')
+    M, N, K = 256, 256, 128
+    for d in (0, 1):
+        with torch.cuda.device(d):
+            A, B = rnd(M, K, seed=11, dtype=BF16).to(f'cuda:{d}'), rnd(N, K, seed=12, dtype=BF16).to(f'cuda:{d}')
+            for dt, tol in ((F32, 2e-5), (BF16, 4e-3)):
+                C = torch.full((M + 3, N + 5), float('nan'), dtype=dt, device=f'cuda:{d}')
+                ops.gemm_nt_tile(A, B, C[:M, :N], 13)
+                err = relmax(C[:M, :N], A.double() @ B.double().t())
+                assert err <= tol, f'gemm tile=13 on cuda:{d} {dt}: rel-max err {err}'
+                assert bool(torch.isnan(C[M:]).all()) and bool(torch.isnan(C[:, N:]).all()), 'GEMM wrote outside its tile'
+
+
 @pytest.mark.parametrize('nb,M,N,K', [(1, 2048, 128, 1024), (1, 100, 512, 520), (3, 300, 384, 264), (2, 1024, 1024, 456), (6, 64, 520, 1000)])
 def test_gemm_nt_ring_tile_automatic_route_every_epilogue(ops, nb, M, N, K):
     """the 4-stage DMA-ring form of the 128 x 128 tile (tile 16) is taken AUTOMATICALLY by every NT launch of <= 256 such tiles with K >= 256 --
