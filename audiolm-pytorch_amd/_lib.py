@@ -156,6 +156,17 @@ SIGNATURES = {
     'alm_conv1d_causal_pre': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'alm_lstm_launches': [_I, _I],
     'alm_lstm_seq': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    'alm_gconv1d_out_len': [_I, _I, _I, _I],
+    'alm_gconv1d_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_gconv1d_dgrad': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_gconv1d_wgrad_ws_floats': [_I, _I, _I, _I, _I, _I, _I, _I],
+    'alm_gconv1d_wgrad': [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_avgpool1d_out_len': [_I, _I],
+    'alm_avgpool1d_fwd': [_P, _P, _L, _I, _I, _P],
+    'alm_avgpool1d_bwd': [_P, _P, _L, _I, _I, _P],
+    'alm_loss_ws_floats': [],
+    'alm_loss_mean_fwd': [_P, _P, _P, _P, _L, _I, _P],
+    'alm_loss_mean_bwd': [_P, _P, _P, _P, _P, _L, _I, _P],
     'alm_memset_zero': [_P, _L, _P],
     'alm_list_op_id': [ctypes.c_char_p],
     'alm_list_op_nargs': [_I],

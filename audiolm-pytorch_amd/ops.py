@@ -1552,3 +1552,107 @@ def lstm_seq(xproj, w_ih, w_hh, bias, *, skip=None, out_bct=False):
     _lib.call('alm_lstm_seq', xproj.data_ptr(), w_ih.data_ptr(), w_hh.data_ptr(), bias.data_ptr(), hseq.data_ptr(), c.data_ptr(), _p(skip), _p(out),
               T, B, H, L, _st())
     return out if out_bct else hseq[L - 1]
+
+
+# ---- wave discriminators of SoundStream training (csrc/discr.hip), fp32, no atomics
+
+LOSS_HINGE_DISCR, LOSS_HINGE_GEN, LOSS_L1, LOSS_MSE = 0, 1, 2, 3
+
+
+def gconv1d_out_len(Tin, ksize, stride, padding):
+    return _lib.query('alm_gconv1d_out_len', Tin, ksize, stride, padding)
+
+
+def _gconv_dims(x, w, stride, padding, groups):
+    B, Cin, Tin = x.shape
+    Cout, cig, K = w.shape
+    assert Cin % groups == 0 and Cout % groups == 0 and cig == Cin // groups, (x.shape, w.shape, groups)
+    Tout = gconv1d_out_len(Tin, K, stride, padding)
+    if Tout < 1:
+        raise _lib.AlmError(f'gconv1d: the padded input ({Tin} + 2 * {padding}) is shorter than the kernel ({K})')
+    return B, Cin, Cout, Tin, K, Tout
+
+
+def gconv1d(x, w, bias, *, stride=1, padding=0, groups=1, leaky=False):
+    """x fp32 [B, Cin, Tin], w fp32 [Cout, Cin / groups, k] (nn.Conv1d layout), bias [Cout] -> act(conv1d(x, w, bias, stride, padding, groups))
+    fp32 [B, Cout, Tout]; leaky: LeakyReLU(0.1)."""
+    assert all(_chk(t, F32).is_contiguous() for t in (x, w, bias))
+    B, Cin, Cout, Tin, K, Tout = _gconv_dims(x, w, stride, padding, groups)
+    y = _new((B, Cout, Tout), dtype=F32, device=x.device)
+    _lib.call('alm_gconv1d_fwd', x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), B, Cin, Cout, Tin, K, stride, padding, groups, int(leaky), _st())
+    return y
+
+
+def gconv1d_dgrad(g, y, w, Cin, Tin, *, stride=1, padding=0, groups=1):
+    """g fp32 [B, Cout, Tout] = dL/dout (times LeakyReLU'(.) taken from the saved output y when y is given) -> dL/dx fp32 [B, Cin, Tin] of gconv1d"""
+    assert all(_chk(t, F32).is_contiguous() for t in (g, w))
+    B, Cout, Tout = g.shape
+    K = w.shape[2]
+    assert w.shape[0] == Cout and Tout == gconv1d_out_len(Tin, K, stride, padding)
+    if y is not None:
+        assert _chk(y, F32).shape == g.shape and y.is_contiguous()
+    dx = _new((B, Cin, Tin), dtype=F32, device=g.device)
+    _lib.call('alm_gconv1d_dgrad', g.data_ptr(), _p(y), w.data_ptr(), dx.data_ptr(), B, Cin, Cout, Tin, K, stride, padding, groups, _st())
+    return dx
+
+
+def gconv1d_wgrad(g, y, x, ksize, *, stride=1, padding=0, groups=1):
+    """g fp32 [B, Cout, Tout] (times LeakyReLU'(.) from y when given), x fp32 [B, Cin, Tin] -> (dW fp32 [Cout, Cin / groups, k], db fp32 [Cout]);
+    per-split partial sums in a workspace of alm_gconv1d_wgrad_ws_floats floats, added in split order."""
+    assert all(_chk(t, F32).is_contiguous() for t in (g, x))
+    B, Cout, Tout = g.shape
+    _, Cin, Tin = x.shape
+    assert x.shape[0] == B and Tout == gconv1d_out_len(Tin, ksize, stride, padding)
+    if y is not None:
+        assert _chk(y, F32).shape == g.shape and y.is_contiguous()
+    n = _lib.query('alm_gconv1d_wgrad_ws_floats', B, Cin, Cout, Tin, ksize, stride, padding, groups)
+    if n < 0:
+        raise _lib.AlmError('gconv1d_wgrad: shape outside the kernel envelope (tile / workspace limits)')
+    ws = _new((n,), dtype=F32, device=g.device)
+    dw = _new((Cout, Cin // groups, ksize), dtype=F32, device=g.device)
+    db = _new((Cout,), dtype=F32, device=g.device)
+    _lib.call('alm_gconv1d_wgrad', g.data_ptr(), _p(y), x.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), n, B, Cin, Cout, Tin, ksize, stride,
+              padding, groups, _st())
+    return dw, db
+
+
+def avgpool1d_out_len(T, f):
+    return _lib.query('alm_avgpool1d_out_len', T, f)
+
+
+def avgpool1d(x, f):
+    """nn.AvgPool1d(2 f, stride=f, padding=f) (padding counts in the divisor) along the last axis of a contiguous fp32 tensor"""
+    assert _chk(x, F32).is_contiguous() and f >= 1
+    T = x.shape[-1]
+    y = _new((*x.shape[:-1], avgpool1d_out_len(T, f)), dtype=F32, device=x.device)
+    _lib.call('alm_avgpool1d_fwd', x.data_ptr(), y.data_ptr(), x.numel() // T, T, f, _st())
+    return y
+
+
+def avgpool1d_bwd(g, T, f):
+    """adjoint of avgpool1d: g [..., T // f + 1] -> [..., T]"""
+    assert _chk(g, F32).is_contiguous() and g.shape[-1] == avgpool1d_out_len(T, f)
+    dx = _new((*g.shape[:-1], T), dtype=F32, device=g.device)
+    _lib.call('alm_avgpool1d_bwd', g.data_ptr(), dx.data_ptr(), dx.numel() // T, T, f, _st())
+    return dx
+
+
+def loss_mean(mode, a, b=None):
+    """0-dim fp32 mean over all elements, summed in a fixed order: LOSS_HINGE_DISCR relu(1 + a) + relu(1 - b) (a fake, b real logits),
+    LOSS_HINGE_GEN -a, LOSS_L1 |a - b|, LOSS_MSE (a - b)^2"""
+    assert _chk(a, F32).is_contiguous() and (b is None) == (mode == LOSS_HINGE_GEN)
+    if b is not None:
+        assert _chk(b, F32).is_contiguous() and b.shape == a.shape
+    out = _new((), dtype=F32, device=a.device)
+    ws = _new((_lib.query('alm_loss_ws_floats'),), dtype=F32, device=a.device)
+    _lib.call('alm_loss_mean_fwd', a.data_ptr(), _p(b), out.data_ptr(), ws.data_ptr(), a.numel(), mode, _st())
+    return out
+
+
+def loss_mean_bwd(mode, a, b, gout, need_a=True, need_b=True):
+    """(d/da | None, d/db | None) of loss_mean given the upstream gradient gout (0-dim fp32, read on the device)"""
+    assert _chk(gout, F32).numel() == 1
+    da = _new_like(a) if need_a else None
+    db = _new_like(b) if need_b and b is not None else None
+    _lib.call('alm_loss_mean_bwd', a.data_ptr(), _p(b), gout.data_ptr(), _p(da), _p(db), a.numel(), mode, _st())
+    return da, db

@@ -2,8 +2,10 @@
 (§8(f) item 3, incl. the LocalTransformer of the reference-default `use_local_attn=True`): `SoundStream.tokenize(audio)`, `SoundStream.forward(x, return_encoded=True |
 return_codes_only=True)` -- the causal-conv encoder (soundstream.py:332-380, 519-531) and the eval-mode forward of the grouped residual VQ
 (soundstream.py:592-607, :840) -- and `decode_from_codebook_indices` / `decode` (soundstream.py:691-709: code lookup, transposed-conv
-decoder :347-360, 382-395, 615-627) run on the MI355X kernels of csrc/codec.hip (exact-fp32 MFMA).  Everything else the reference class
-does (discriminators, losses, LFQ / FSQ quantizers) is out of scope and raises.  In training mode the quantizer takes one
+decoder :347-360, 382-395, 615-627) run on the MI355X kernels of csrc/codec.hip (exact-fp32 MFMA).  The training losses (soundstream.py:868-995:
+three wave MultiScaleDiscriminators, hinge / feature / reconstruction terms) are opt-in, `with_discriminators=True` (discriminators.py,
+csrc/discr.hip); the default ComplexSTFTDiscriminator, the mel-spectrogram loss, the gradient penalty and the LFQ / FSQ quantizers are out of scope
+and raise.  In training mode the quantizer takes one
 training step per call (csrc/rvq_train.hip: quantize dropout, commitment loss, rotation trick, EMA codebooks with dead-code expiry, k-means
 initialisation; single process only), so `forward(x, return_recons_only=True | return_encoded=True)` is differentiable end to end.  The conv encoder / decoder are
 differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
@@ -34,7 +36,7 @@ from itertools import cycle
 import torch
 from torch import nn
 
-from . import codec_bwd, core, ops
+from . import codec_bwd, core, discriminators as D, ops
 from .resample import resample
 
 F32 = torch.float32
@@ -540,9 +542,11 @@ class SoundStream(nn.Module):
     def __init__(self, *, channels=32, strides=(2, 4, 5, 8), channel_mults=(2, 4, 8, 16), codebook_dim=512, codebook_size=None,
                  finite_scalar_quantizer_levels=None, rq_num_quantizers=8, rq_commitment_weight=1., rq_ema_decay=0.95,
                  rq_quantize_dropout_multiple_of=1, rq_groups=1, rq_stochastic_sample_codes=False, rq_rotation_trick=True, rq_kwargs: dict = {},
-                 use_lookup_free_quantizer=False, use_finite_scalar_quantizer=False, input_channels=1, enc_cycle_dilations=(1, 3, 9),
-                 target_sample_hz=16000, use_local_attn=True, attn_window_size=128, attn_dim_head=64, attn_heads=8, attn_depth=1,
-                 attn_xpos_scale_base=None, attn_dynamic_pos_bias=False, use_gate_loop_layers=False, squeeze_excite=False, pad_mode='reflect', **kwargs):
+                 use_lookup_free_quantizer=False, use_finite_scalar_quantizer=False, input_channels=1, discr_multi_scales=(1, 0.5, 0.25),
+                 enc_cycle_dilations=(1, 3, 9), recon_loss_weight=1., multi_spectral_recon_loss_weight=1e-5, adversarial_loss_weight=1.,
+                 feature_loss_weight=100, target_sample_hz=16000, use_local_attn=True, attn_window_size=128, attn_dim_head=64, attn_heads=8, attn_depth=1,
+                 attn_xpos_scale_base=None, attn_dynamic_pos_bias=False, use_gate_loop_layers=False, squeeze_excite=False, pad_mode='reflect',
+                 stft_discriminator=None, with_discriminators=False, **kwargs):
         super().__init__()
         if use_lookup_free_quantizer or use_finite_scalar_quantizer or finite_scalar_quantizer_levels is not None:
             raise NotImplementedError('LFQ / FSQ quantizers are out of scope (SURVEY.md §2)')
@@ -575,11 +579,31 @@ class SoundStream(nn.Module):
                                     quantize_dropout_cutoff_index=kwargs.get('quantize_dropout_cutoff_index', 1),
                                     quantize_dropout_multiple_of=rq_quantize_dropout_multiple_of, rotation_trick=rq_rotation_trick, kmeans_iters=10,
                                     threshold_ema_dead_code=2)                                           # soundstream.py:592-607 (rq_kwargs: ignored, like before)
+        # the training losses (soundstream.py:629-679) are opt-in: without `with_discriminators=True` nothing below is registered and the loss
+        # branches of forward raise, like before
+        self.with_discriminators = bool(with_discriminators)
+        self.discr_multi_scales = discr_multi_scales
+        self.recon_loss_weight, self.multi_spectral_recon_loss_weight = recon_loss_weight, multi_spectral_recon_loss_weight
+        self.adversarial_loss_weight, self.feature_loss_weight = adversarial_loss_weight, feature_loss_weight
+        self._stft_discriminator_off = stft_discriminator is False
+        if self.with_discriminators:
+            self.discriminators = nn.ModuleList([D.MultiScaleDiscriminator() for _ in range(len(discr_multi_scales))])
+            factors = [int(s1 / s2) for s1, s2 in zip(discr_multi_scales[:-1], discr_multi_scales[1:])]
+            self.downsamples = nn.ModuleList([nn.Identity()] + [D.AvgPoolDownsample(f) for f in factors])
+            if isinstance(stft_discriminator, nn.Module):
+                self.stft_discriminator = stft_discriminator     # the caller's module, run by PyTorch as it is
+            elif stft_discriminator not in (None, False):
+                raise TypeError('stft_discriminator: an nn.Module with forward(x, return_intermediates=False), False (train without one) or None')
         self.eval()
 
     @property
     def device(self):
         return next(self.parameters()).device
+
+    def non_discr_parameters(self):                              # soundstream.py:760-769 (the FiLM conditioners do not exist here)
+        return [*self.encoder.parameters(), *self.decoder.parameters(),
+                *(self.encoder_attn.parameters() if self.encoder_attn is not None else []),
+                *(self.decoder_attn.parameters() if self.decoder_attn is not None else []), *self.rq.parameters()]
 
     @property
     def seq_len_multiple_of(self):                               # soundstream.py:772-774
@@ -625,12 +649,19 @@ class SoundStream(nn.Module):
         """The codec branches of soundstream.py:802-862 (same positional order): return_codes_only -> indices (g, b, n, q);
         return_encoded -> (quantized, indices 'b n (g q)', commit_loss (g, q)); return_recons_only -> the reconstructed wave.  In eval mode
         nothing is recorded for autograd and commit_loss is zero; in training mode the quantizer takes one training step (GroupedResidualVQ) and,
-        with grad mode on, the results carry a graph through encoder, quantizer and decoder.  The loss branches (discriminators, adversarial /
-        feature / mel losses) are out of scope and raise."""
-        if target is not None or is_denoising is not None or return_discr_loss or return_discr_losses_separately or return_loss_breakdown \
-                or apply_grad_penalty or not (return_encoded or return_codes_only or return_recons_only):
+        with grad mode on, the results carry a graph through encoder, quantizer and decoder.  The loss branches (soundstream.py:868-995) need
+        `with_discriminators=True` at construction and raise without it: return_discr_loss (with return_discr_losses_separately: the list of
+        ('scale:{s}', loss) / ('stft', loss) pairs) works on the input and the detached reconstruction; otherwise the generator's total loss, with
+        return_loss_breakdown also (recon, multi_spectral, adversarial, feature, commitment).  `target=` replaces the input in the recon term."""
+        codec_only = return_encoded or return_codes_only or return_recons_only
+        if not self.with_discriminators and (target is not None or is_denoising is not None or return_discr_loss or return_discr_losses_separately
+                                             or return_loss_breakdown or apply_grad_penalty or not codec_only):
             raise NotImplementedError('only forward(..., return_codes_only=True | return_encoded=True | return_recons_only=True) is implemented '
-                                      '(the discriminators and the losses of SoundStream training are out of scope)')
+                                      'on a SoundStream built without with_discriminators=True (the training losses are opt-in)')
+        if is_denoising is not None:
+            raise NotImplementedError('is_denoising (the FiLM conditioners of the denoising variant) is not implemented')
+        if not codec_only:
+            self._check_loss_options(apply_grad_penalty)
         with torch.set_grad_enabled(torch.is_grad_enabled() and self.training):
             x, lead = self.process_input(x, input_sample_hz=input_sample_hz, curtail_from_left=curtail_from_left)
             feats = self.encode(x)
@@ -641,7 +672,72 @@ class SoundStream(nn.Module):
             if return_encoded:
                 return quantized, indices.permute(1, 2, 0, 3).reshape(b, n, -1), commit_loss          # 'g b n q -> b n (g q)', :851
             recon = self.decode(quantized)                           # :857-866, unpack(recon_x, ps, '* c n')
-            return recon.reshape(*lead, recon.shape[-2], recon.shape[-1])
+            if return_recons_only:
+                return recon.reshape(*lead, recon.shape[-2], recon.shape[-1])
+            orig_x = x.to(F32).contiguous()
+            if return_discr_loss:
+                return self._discr_loss(orig_x, recon.detach(), return_discr_losses_separately)
+            if target is not None:
+                target, _ = self.process_input(target, input_sample_hz=input_sample_hz, curtail_from_left=curtail_from_left)
+            return self._generator_loss(orig_x, recon, orig_x if target is None else target.to(F32).contiguous(), commit_loss, return_loss_breakdown)
+
+    def _check_loss_options(self, apply_grad_penalty):
+        """the three parts of the reference's losses that are not built, each by name, before any launch"""
+        if self.multi_spectral_recon_loss_weight > 0:
+            raise NotImplementedError('the multi-spectral mel-spectrogram reconstruction loss (torchaudio MelSpectrogram) is not implemented: construct '
+                                      'the SoundStream with multi_spectral_recon_loss_weight=0')
+        if apply_grad_penalty:
+            raise NotImplementedError('apply_grad_penalty=True (gradient penalty) needs a double backward through the discriminator kernels, which is '
+                                      'not implemented')
+        if getattr(self, 'stft_discriminator', None) is None and not self._stft_discriminator_off:
+            raise NotImplementedError('the default ComplexSTFTDiscriminator is not implemented: pass stft_discriminator=<an nn.Module with '
+                                      'forward(x, return_intermediates=False)>, or stft_discriminator=False to train without one')
+
+    def _scales(self, real, fake):
+        """per wave discriminator (logits, intermediates) of real and fake run as ONE batch [real | fake] through the chain of downsamples"""
+        b = real.shape[0]
+        scaled = torch.cat((real, fake), dim=0)
+        for discr, downsample in zip(self.discriminators, self.downsamples):
+            scaled = downsample(scaled)
+            logits, inter = discr(scaled, return_intermediates=True)
+            yield (logits[:b], logits[b:]), [(t[:b], t[b:]) for t in inter]
+
+    def _discr_loss(self, real, fake, separately):               # soundstream.py:870-925 (without the gradient penalties)
+        stft_loss = None
+        if not self._stft_discriminator_off and self.single_channel:
+            stft_real_logits, stft_fake_logits = self.stft_discriminator(real), self.stft_discriminator(fake)
+            stft_loss = D.hinge_discr_loss(stft_fake_logits, stft_real_logits)
+        losses = [D.hinge_discr_loss(fake_logits, real_logits) for (real_logits, fake_logits), _ in self._scales(real, fake)]
+        if not separately:
+            total = torch.stack(losses).mean()
+            return total if stft_loss is None else total + stft_loss
+        pkg = [(f'scale:{scale}', loss) for scale, loss in zip(self.discr_multi_scales, losses)]
+        if stft_loss is not None:
+            pkg.append(('stft', stft_loss))
+        return pkg
+
+    def _generator_loss(self, real, fake, target, commit_loss, breakdown):      # soundstream.py:927-995
+        recon_loss = D.mse_loss(target, fake)
+        multi_spectral_recon_loss = torch.zeros((), dtype=F32, device=real.device)
+        adversarial, pairs = [], []
+        stft_fake_logits = None
+        if not self._stft_discriminator_off:
+            _, stft_real_inter = self.stft_discriminator(real, return_intermediates=True)
+            stft_fake_logits, stft_fake_inter = self.stft_discriminator(fake, return_intermediates=True)
+            pairs.extend(zip(stft_real_inter, stft_fake_inter))
+        for (_, fake_logits), inter in self._scales(real, fake):
+            adversarial.append(D.hinge_gen_loss(fake_logits))
+            pairs.extend(inter)
+        feature_loss = torch.stack([D.l1_loss(r, f) for r, f in pairs]).mean()
+        if stft_fake_logits is not None:
+            adversarial.append(D.hinge_gen_loss(stft_fake_logits))
+        adversarial_loss = torch.stack(adversarial).mean()
+        all_commitment_loss = commit_loss.sum()
+        total = recon_loss * self.recon_loss_weight + multi_spectral_recon_loss * self.multi_spectral_recon_loss_weight \
+            + adversarial_loss * self.adversarial_loss_weight + feature_loss * self.feature_loss_weight + all_commitment_loss
+        if breakdown:
+            return total, (recon_loss, multi_spectral_recon_loss, adversarial_loss, feature_loss, all_commitment_loss)
+        return total
 
     def decode_from_codebook_indices(self, quantized_indices):               # soundstream.py:691-699
         assert quantized_indices.dtype in (torch.long, torch.int32)

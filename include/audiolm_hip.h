@@ -569,6 +569,36 @@ int alm_lstm_launches(int T, int L);
 int alm_lstm_seq(const float* xproj, const float* w_ih, const float* w_hh, const float* bias, float* hseq, float* c, const float* skip, float* out,
                  int T, int B, int H, int L, void* stream);
 
+/* ---- wave discriminators of SoundStream training (csrc/discr.hip), fp32, no atomics ---------------------------------------------------------------
+ * Grouped strided zero-padded conv1d, y = act(conv1d(x, w, bias, stride, padding, groups)) with act 0 = identity, 1 = LeakyReLU(0.1)
+ * (reference soundstream.py:92-140).  x [B][Cin][Tin], w [Cout][Cin / groups][k] (nn.Conv1d's layout, read as it is), y [B][Cout][Tout],
+ * Tout = alm_gconv1d_out_len = (Tin + 2 padding - k) / stride + 1 (-1 when the padded input is shorter than the kernel).
+ *   alm_gconv1d_dgrad : dx [B][Cin][Tin] from g = dL/dy; y = the saved OUTPUT of an act = 1 layer (g is multiplied by 1 where y > 0, else 0.1) or null.
+ *   alm_gconv1d_wgrad : dw [Cout][Cin / groups][k], db [Cout]; partial sums per split of the (batch, 64-step chunk) list into ws
+ *                       (alm_gconv1d_wgrad_ws_floats floats, caller-owned; -1: outside the kernel's envelope), then added in split order.
+ * alm_avgpool1d_* : AvgPool1d(2 f, stride f, padding f), count_include_pad; x [rows][T] -> y [rows][T / f + 1] (alm_avgpool1d_out_len) and its adjoint.
+ * alm_loss_mean_fwd : out[0] = mean of the mode's term over n elements, summed in a fixed order (ws: alm_loss_ws_floats floats):
+ *     ALM_LOSS_HINGE_DISCR relu(1 + a) + relu(1 - b) (a = fake, b = real logits), ALM_LOSS_HINGE_GEN -a (b unused), ALM_LOSS_L1 |a - b|, ALM_LOSS_MSE (a - b)^2.
+ * alm_loss_mean_bwd : da, db (either may be null) = gout[0] / n * d term / d a, d b; gout is read from device memory. */
+#define ALM_LOSS_HINGE_DISCR 0
+#define ALM_LOSS_HINGE_GEN 1
+#define ALM_LOSS_L1 2
+#define ALM_LOSS_MSE 3
+int alm_gconv1d_out_len(int Tin, int ksize, int stride, int padding);
+int alm_gconv1d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int Tin, int ksize, int stride, int padding,
+                    int groups, int act, void* stream);
+int alm_gconv1d_dgrad(const float* g, const float* y, const float* w, float* dx, int B, int Cin, int Cout, int Tin, int ksize, int stride, int padding,
+                      int groups, void* stream);
+int alm_gconv1d_wgrad_ws_floats(int B, int Cin, int Cout, int Tin, int ksize, int stride, int padding, int groups);
+int alm_gconv1d_wgrad(const float* g, const float* y, const float* x, float* dw, float* db, float* ws, long long ws_floats, int B, int Cin, int Cout,
+                      int Tin, int ksize, int stride, int padding, int groups, void* stream);
+int alm_avgpool1d_out_len(int T, int f);
+int alm_avgpool1d_fwd(const float* x, float* y, long long rows, int T, int f, void* stream);
+int alm_avgpool1d_bwd(const float* g, float* dx, long long rows, int T, int f, void* stream);
+int alm_loss_ws_floats(void);
+int alm_loss_mean_fwd(const float* a, const float* b, float* out, float* ws, long long n, int mode, void* stream);
+int alm_loss_mean_bwd(const float* a, const float* b, const float* gout, float* da, float* db, long long n, int mode, void* stream);
+
 /* ---- launch lists (round 6): a recorded sequence of the launches above re-issued by ONE host call ---------------------------------------------
  * The depth loop of audiolm_pytorch.py:528-547 (Transformer.forward) and its backward are ~190 launches per training step whose ORDER and scalar arguments
  * depend only on the model configuration and the batch shape; only buffer addresses change between steps.  The host records the sequence once per shape

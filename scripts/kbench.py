@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr]"""
 import os
 import sys
 import time
@@ -673,6 +673,97 @@ def bench_rvq_train():
               f'counts equal {bool(torch.equal(n, rn))}  max rel diff of the sums {relerr(s, rs):.1e}')
     print(f'rvq_train forward {M} frames x {Q} x {C} codes, d {d}: {t_fwd:.2f} ms   eval alm_rvq_encode {t_eval:.2f} ms   forward / eval {t_fwd / t_eval:.2f}   '
           f'backward {t_bwd:.2f} ms')
+
+
+def bench_discr():
+    """wave discriminators of SoundStream training at 8 x 1 s and 8 x 10 s of 16 kHz audio (real and fake as one batch of 16): forward + backward of one
+    MultiScaleDiscriminator (input and parameter gradients), each of its seven layers alone, and the whole discriminator-loss step (three scales, the
+    pooling between them, hinge means, backward into all 16.9 M parameters) on the kernels of csrc/discr.hip, against the SAME modules run by PyTorch-ROCm
+    (F.conv1d / F.leaky_relu / F.avg_pool1d / F.relu, fp32) on the same box.  Interleaved: each round times the hand path, then ATen; medians of the
+    rounds, one event pair per call."""
+    import torch.nn.functional as F
+    from audiolm_pytorch_amd import discriminators as D
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def pair(ours, aten, rounds=10, warm=2):
+        for _ in range(warm):
+            ours(), aten()
+        torch.cuda.synchronize()
+        a, b = [], []
+        for _ in range(rounds):
+            a.append(once(ours)), b.append(once(aten))
+        a.sort(), b.sort()
+        return a[len(a) // 2], b[len(b) // 2]
+
+    def aten_discr(m, x):
+        x = m.init_conv(x)
+        inter = []
+        for layer in m.conv_layers:
+            x = F.leaky_relu(layer[0](x), 0.1)
+            inter.append(x)
+        return m.final_conv[2](F.leaky_relu(m.final_conv[0](x), 0.1)), inter
+
+    def fwd_bwd(run, m, x):
+        logits, inter = run(m, x)
+        loss = logits.mean() + sum(t.mean() for t in inter)
+        torch.autograd.grad(loss, [x, *m.parameters()])
+
+    torch.manual_seed(0)
+    discrs = [A.MultiScaleDiscriminator().to(dev) for _ in range(3)]
+    downs = [None, D.AvgPoolDownsample(2), D.AvgPoolDownsample(2)]
+    m = discrs[0]
+    for secs in (1, 10):
+        T = 16000 * secs
+        real, fake = torch.randn(8, 1, T, device=dev) * 0.3, torch.randn(8, 1, T, device=dev) * 0.3
+        x = torch.cat((real, fake)).requires_grad_()
+        t_o, t_a = pair(lambda: fwd_bwd(lambda mm, xx: mm(xx, return_intermediates=True), m, x), lambda: fwd_bwd(aten_discr, m, x))
+        print(f'discr 8 x {secs} s: one MultiScaleDiscriminator fwd + bwd (batch 16 x {T}): hand {t_o:.2f} ms   ATen {t_a:.2f} ms   hand / ATen {t_o / t_a:.2f}', flush=True)
+        h = x.detach()
+        convs = [('init_conv', m.init_conv, False), *((f'conv_layers.{i}', l[0], True) for i, l in enumerate(m.conv_layers)),
+                 ('final_conv.0', m.final_conv[0], True), ('final_conv.2', m.final_conv[2], False)]
+        for name, conv, leaky in convs:
+            hin = h.clone().requires_grad_()
+
+            def ours_layer():
+                y = D.conv1d_act(conv, hin, leaky=leaky)
+                torch.autograd.grad(y.mean(), [hin, conv.weight, conv.bias])
+
+            def aten_layer():
+                y = conv(hin)
+                y = F.leaky_relu(y, 0.1) if leaky else y
+                torch.autograd.grad(y.mean(), [hin, conv.weight, conv.bias])
+            t_o, t_a = pair(ours_layer, aten_layer, rounds=6)
+            print(f'    {name:14s} {conv.in_channels:5d} -> {conv.out_channels:5d} k{conv.kernel_size[0]} s{conv.stride[0]} g{conv.groups:<4d} T_in {hin.shape[-1]:7d}: '
+                  f'hand {t_o:.3f} ms   ATen {t_a:.3f} ms   hand / ATen {t_o / t_a:.2f}', flush=True)
+            with torch.no_grad():
+                h = D.conv1d_act(conv, hin.detach(), leaky=leaky)
+        params = [p for d in discrs for p in d.parameters()]
+
+        def ours_step():
+            scaled, losses = torch.cat((real, fake)), []
+            for d, down in zip(discrs, downs):
+                scaled = scaled if down is None else down(scaled)
+                logits = d(scaled)
+                losses.append(D.hinge_discr_loss(logits[8:], logits[:8]))
+            torch.autograd.grad(torch.stack(losses).mean(), params)
+
+        def aten_step():
+            r, f, losses = real, fake, []
+            for d, down in zip(discrs, downs):
+                if down is not None:
+                    r, f = F.avg_pool1d(r, 4, stride=2, padding=2), F.avg_pool1d(f, 4, stride=2, padding=2)
+                rl, fl = aten_discr(d, r)[0], aten_discr(d, f)[0]
+                losses.append((F.relu(1 + fl) + F.relu(1 - rl)).mean())
+            torch.autograd.grad(torch.stack(losses).mean(), params)
+        t_o, t_a = pair(ours_step, aten_step)
+        print(f'discr 8 x {secs} s: discriminator-loss step (3 scales, fwd + bwd): hand {t_o:.2f} ms   ATen {t_a:.2f} ms   hand / ATen {t_o / t_a:.2f}', flush=True)
 
 
 if __name__ == '__main__':
