@@ -31,6 +31,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "gemm_plan.hpp"
 #include "../../include/audiolm_hip.h"
 
 // Cache policy of the operand DMA (`buffer_load ... lds` aux immediate: 1 = sc0, 2 = nt, 16 = sc1).  0 in the product build; scripts/build_variant.sh
@@ -42,9 +43,9 @@
 #define ALM_GEMM_AUX_B 0
 #endif
 
+using namespace gemm_plan;         // the host arithmetic: hooks (GemmEnv), tile choice, split-K / hybrid / grouped plans, operand checks
 namespace {
 
-constexpr int BK = 64;
 constexpr unsigned OOB = 0x80000000u;         // buffer offset beyond every num_records: the DMA returns zeros
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -816,8 +817,7 @@ __global__ __launch_bounds__(512) void gemm_stag_group2_kernel(GemmParams p0, Ge
 // operands, so a unit's workgroups sit next to one another on ONE XCD (one L2).  Units are numbered job by job, u = base[j] + problem * S + slice, and dealt
 // round-robin over the 8 XCDs (unit u on XCD u % 8; workgroup b runs on XCD b % 8 and is slot b / 8 of that XCD's list), which balances the XCDs to within one
 // unit per job.  Every workgroup finds its (job, problem, slice, tile) from the small table below: scalar arithmetic, no memory but the kernel arguments.
-constexpr int TN_GROUP_MAX = 8;
-struct TnGroupTable {
+struct TnGroupTable {                   // (the four placement arrays + njobs, S: TnGroupPlacement of gemm_plan.hpp, filled by tn_group_geometry)
     GemmParams p[TN_GROUP_MAX];
     int tiles[TN_GROUP_MAX];            // tiles of ONE problem of the job (tiles_m x tiles_n)
     int tiles_n[TN_GROUP_MAX];
@@ -826,13 +826,6 @@ struct TnGroupTable {
     int njobs, S;
 };
 static_assert(sizeof(TnGroupTable) <= 3800, "kernel-argument segment");
-
-// workgroups of XCD x's list that belong to a job whose units are [base, base + n): those numbered == x (mod 8); `first` = the lowest of them
-__host__ __device__ __forceinline__ int tn_group_units_on(int base, int n, int x, int* first) {
-    const int f = base + ((x - base) & 7);
-    *first = f;
-    return f < base + n ? (base + n - 1 - f) / 8 + 1 : 0;
-}
 
 __global__ __launch_bounds__(512) void gemm_tn_grouped_kernel(TnGroupTable g) {
     const int x = (int)blockIdx.x & 7;
@@ -1425,139 +1418,45 @@ int launch_w4(const GemmParams& p, int ny, int nz, hipStream_t st) {
     return alm_launch_raster<256, 256, 256, 131072>(gemm_w4_kernel<TNMODE, OUT_F32>, p, p.raster >= 1, p.plimit, ny, nz, st);
 }
 
-// Tile ids (alm_gemm_bf16_nt_tile): 1 = 128 x 128 (4 waves, two workgroups per CU), 2 = 256 x 256 lock-step (8 waves), 13 = 256 x 256 with
-// staggered wave rows (the production big tile), 11 = 384 x 256 (8 waves, wave tile 192 x 64: 17 % fewer L2 -> LDS bytes per flop), 17 = 320 x 256 (round 6).
-// Automatic choice (tile 0): small problems -> 1; otherwise 13, except that an NT problem takes 11 when the coarser tiling needs so many
-// fewer rounds of 256 resident workgroups that it wins despite its 1.5x longer tile (measured per-tile cost ratio 1.41: W1 forward
-// 16384 x 5472: 6 rounds -> 4, +6 %; with N = 1024 it is 172 tiles on 256 CUs, -15 %).
-int pick_tile(int M, int N, int ny, int tile, bool tn) {
-    if (tile == 1 || tile == 2 || tile == 11 || tile == 13 || tile == 14 || tile == 15 || tile == 16 || tile == 17) return tile;
-    if (tile != 0) return -1;
-    if (M < 256 || N < 256) return 1;
-    const long long t256 = (long long)((M + 255) / 256) * ((N + 255) / 256) * ny;
-    if (t256 < 192) return 1;               // not enough 256^2 tiles to occupy most of the 256 CUs
-    if (!tn) {
-        // round model over the three big tiles: rounds of 256 resident workgroups x measured cost of one tile relative to 256 x 256 (384 x 256: 1.41).  Round 6:
-        // 320 x 256 (tile 17, the generic 8-wave kernel with a 160 x 64 wave tile) for RAGGED token counts -- FineTransformer N = 2049, B = 8: M = 16 392 is 65 tile
-        // rows of 256, so an N = 1024 output is 260 tiles = TWO rounds; 384 x 256 makes it 172 tiles (one round at 67 % of the CUs), 320 x 256 makes it 208
-        // (one round at 81 %, shorter tiles).  ALM_GEMM_T320_COST (x 100, default 122; 0 = never) is its relative cost in the model.
-        static const double c320 = [] { const char* e = getenv("ALM_GEMM_T320_COST"); return e ? atoi(e) / 100.0 : 1.22; }();
-        const long long t384 = (long long)((M + 383) / 384) * ((N + 255) / 256) * ny;
-        const long long t320 = (long long)((M + 319) / 320) * ((N + 255) / 256) * ny;
-        const double c13 = (double)((t256 + 255) / 256), c11 = (double)((t384 + 255) / 256) * 1.41;
-        const double c17 = c320 > 0. ? (double)((t320 + 255) / 256) * c320 : 1e30;
-        if (c17 < c13 && c17 < c11) return 17;
-        if (c11 < c13) return 11;
-    }
-    return 13;
-}
-
 // Rasterisation group of a raster-0 launch (GemmParams::group_m).  An XCD's L2 (4 MiB) serves the ~32 tiles its CUs run at a time: with groups of g
 // tile rows those are g x (32 / g) tiles, and the group's A panel (g x BM rows x K) is what successive tile columns re-read -- it should FIT the L2
 // beside the streaming B tiles.  ALM_GEMM_GROUP_M=<g> (A/B runs) overrides; negative = groups of tile columns.
-int pick_group(const GemmParams& p, int tl) {
-    static const int env_g = [] { const char* e = getenv("ALM_GEMM_GROUP_M"); return e ? atoi(e) : 0; }();
-    if (env_g != 0) return env_g;
-    (void)p; (void)tl;
-    return 8;
-}
+int pick_group() { return gemm_env().group_m != 0 ? gemm_env().group_m : 8; }
 
+// the tail of every entry point: a launcher's own error, else what the runtime reports for the launch
+int checked(int rc) { return rc ? rc : (int)hipGetLastError(); }
+
+// one launch on the tile final_tile() names (gemm_plan.hpp: pick_tile, the A/B hooks and the reroutes -- the plan queries ask the same function)
 template <bool TNMODE>
 int launch_gemm(const GemmParams& p0, int ny, int nz, int out_f32, int tile, hipStream_t st, bool hook = true, bool only256 = false) {
-    static const int big_tile = [] { const char* e = getenv("ALM_GEMM_BIG_TILE"); return e ? atoi(e) : 0; }();   // A/B hook: 2 / 11 / 13 for every big launch
-    static const int nt_store = [] { const char* e = getenv("ALM_GEMM_NT_STORE"); return e ? atoi(e) : 0; }();    // A/B hook: non-temporal C stores
+    const int nt_store = gemm_env().nt_store;
     GemmParams p = p0;
-    int tl = pick_tile(p.M, p.N, ny * nz, tile, TNMODE);
+    const int tl = final_tile(TNMODE, p.M, p.N, p.ksplit > 0 ? p.ksplit : p.K, ny, nz, tile, hook, only256, p.ksplit != 0, p.raster);
     if (tl < 0) return ALM_ERR_UNSUPPORTED;
-    p.group_m = pick_group(p, tl);
+    p.group_m = pick_group();
     p.nt_store = (nt_store == 1 || (nt_store == 2 && !out_f32)) ? 1 : 0;
-    // only256: the caller's panel arithmetic (GemmParams.plimit and the tail offset of the hybrid weight-gradient plan) is in units of 256 x 256 tiles --
-    // the hook may swap the 256 x 256 kernels for one another there, never re-tile the launch (a 384 x 256 grid would cover the wrong set of C tiles)
-    if (hook && tl != 1 && (big_tile == 2 || big_tile == 13 || big_tile == 14 || (big_tile == 11 && !only256))) tl = big_tile;
-    // The 4-wave tile (gemm_w4_kernel, id 14) is OPT-IN: stand-alone its main loop is 4-9 % faster per K-step than the staggered tile on long
-    // contractions (K = 1024 -1 %, 2736 +-0, 5472 +4 %, 8192 +6-9 %), but INSIDE the training step it measured slower on alternating runs
-    // (ALM_GEMM_W4_MINK = 4096: NT big-tile time 3.94 -> 4.05 ms / step; 2048: 4.13 ms; TN unchanged) -- one wave per SIMD has nothing to cover a
-    // late operand fetch with when the inputs come from HBM instead of a warm L2.  ALM_GEMM_W4_MINK=<K> routes the
-    // automatic 256 x 256 choices with at least that many K elements per slice to it (A/B runs).
-    static const int w4_mink = [] { const char* e = getenv("ALM_GEMM_W4_MINK"); return e ? atoi(e) : 0; }();
-    if (hook && w4_mink > 0 && tl == 13 && tile == 0 && (p.ksplit > 0 ? p.ksplit : p.K) >= w4_mink) tl = 14;
-    // ... except the full-K weight-gradient launches of the hybrid plan (TN, K = all tokens of the batch, no slices): there the 4-wave tile is ON by
-    // default -- its longer uninterrupted main loop is what it was built for: -0.05 ms / step on three interleaved runs (ALM_GEMM_W4_TN_MINK=0: off)
-    static const int w4_tn_mink = [] { const char* e = getenv("ALM_GEMM_W4_TN_MINK"); return e ? atoi(e) : 8192; }();
-    if (TNMODE && hook && w4_tn_mink > 0 && tl == 13 && (p.ksplit > 0 ? p.ksplit : p.K) >= w4_tn_mink) tl = 14;
-    if (tl == 14) return out_f32 ? launch_w4<TNMODE, true>(p, ny, nz, st) : launch_w4<TNMODE, false>(p, ny, nz, st);
-    if (tl == 13) return out_f32 ? launch_stag<TNMODE, true>(p, ny, nz, st) : launch_stag<TNMODE, false>(p, ny, nz, st);
-    // tile 15 (round 5 experiment): 256 x 128, 8 waves as 4 x 2 (wave tile 64 x 64), one workgroup per CU -- for the N = 512 projections (Wq forward, dAO):
-    // 64 x 4 = 256 tiles = ONE round of the chip where the 128 x 128 tile runs 512 workgroups at twice the L2 -> LDS bytes per flop.
-    // ALM_GEMM_MID_TILE=1 routes the automatic small-tile choices with N >= 512 and >= 192 such tiles to it (NT only)
-    static const int mid_tile = [] { const char* e = getenv("ALM_GEMM_MID_TILE"); return e ? atoi(e) : 0; }();
-    if (!TNMODE && hook && mid_tile && tl == 1 && tile == 0 && p.ksplit == 0 && p.M >= 256 && p.N >= 512 &&
-        (long long)((p.M + 255) / 256) * ((p.N + 127) / 128) * ny >= 192) tl = 15;
-    // tile 16 (round 5): the 128 x 128 tile with a 4-stage DMA ring, for NT launches of so few tiles that every CU holds at most one workgroup anyway
-    // (to_kv: 128) -- there the two-stage loop waits for one memory round trip per K-step.  ALM_GEMM_RING=0: off (A/B)
-    static const int ring_on = [] { const char* e = getenv("ALM_GEMM_RING"); return e ? atoi(e) : 1; }();
-    if (!TNMODE && hook && ring_on && tl == 1 && tile == 0 && p.ksplit == 0 && p.raster == 0 && p.K >= 256 &&
-        (long long)((p.M + 127) / 128) * ((p.N + 127) / 128) * ny * nz <= 256) tl = 16;
-    if (tl == 16) { if (TNMODE || p.raster != 0) return ALM_ERR_UNSUPPORTED; return out_f32 ? launch_ring<true>(p, ny, nz, st) : launch_ring<false>(p, ny, nz, st); }
-    if (tl == 15) return out_f32 ? launch_cfg<256, 128, 4, 2, TNMODE, true>(p, ny, nz, st) : launch_cfg<256, 128, 4, 2, TNMODE, false>(p, ny, nz, st);
-    if (tl == 11) return out_f32 ? launch_cfg<384, 256, 2, 4, TNMODE, true>(p, ny, nz, st) : launch_cfg<384, 256, 2, 4, TNMODE, false>(p, ny, nz, st);
-    if (tl == 17) { if (TNMODE) return ALM_ERR_UNSUPPORTED; return out_f32 ? launch_cfg<320, 256, 2, 4, false, true>(p, ny, nz, st) : launch_cfg<320, 256, 2, 4, false, false>(p, ny, nz, st); }
-    if (tl == 2) return out_f32 ? launch_cfg<256, 256, 2, 4, TNMODE, true>(p, ny, nz, st) : launch_cfg<256, 256, 2, 4, TNMODE, false>(p, ny, nz, st);
-    return out_f32 ? launch_cfg<128, 128, 2, 2, TNMODE, true>(p, ny, nz, st) : launch_cfg<128, 128, 2, 2, TNMODE, false>(p, ny, nz, st);
-}
-
-bool view_too_big(long long rows, long long ld) { return rows * ld * 2 >= 0x7fffffffLL; }
-
-// ---- NT launches that cannot fill the chip with 256 x 256 tiles (round 6): in-launch split-K on the staggered tile ----------------------------------------
-// pick_tile() sends every NT launch with < 192 tiles of 256 x 256 to the 128 x 128 tile (twice the L2 -> LDS bytes per flop).  With a caller-owned workspace
-// the alternative is the staggered 256 x 256 tile with each tile's K range cut over S workgroups (gemm_stag_inl_kernel): tiles x S <= 256 workgroups = ONE
-// resident round of the chip.  MEASURED on MI355X (scripts/ab_nt_inl.py, every launch on a fresh operand set; profiles/r6a_nt_inl_cost.log, r6b_*):
-//   * a half-empty chip is NOT half as fast: one K-step of a 256 x 256 workgroup takes 1.2 us with 32 workgroups in flight, 1.6 us with 128, 2.0 us with 256
-//     (L2 / fabric contention), so cutting K in two over twice the workgroups saves ~35 %, not 50 %, of the main loop;
-//   * the publish + reduce is a BURST: every workgroup ends at the same time and writes its 256-KiB slab through to memory -- 16 us with 128 workgroups (32 MB),
-//     24 us with 256 (64 MB) -- and the 128 x 128 tile it competes with runs at 0.25-0.31 of the MFMA peak on these shapes (2 workgroups per CU, all CUs busy).
-//   Net: the split wins only on LONG contractions -- M = 8192, N = 1024, K = 5472 (dXN = dU W1): 116 -> 107 us; K = 2736: 66 vs 68 us (tie); K <= 1024: the
-//   128 x 128 tile wins by 1.5-2x (to_q at M = 16384: 24.5 vs 45.6 us).  A 256 x 128 tile (one round of 256 workgroups for N = 1024) measured 0-14 % SLOWER than
-//   the 128 x 128 tile on every shape.  The model below reproduces those decisions; its constants are the fitted ones:
-//     t(256^2, S >= 2) = ceil(ksteps / S) * (1.15 + 0.0033 W) + 7 + (8 + 0.04 W) + 2.6 * slabs read        [us; W = tiles x S workgroups]
-//     t(128^2)         = rounds of 512 resident workgroups * (ksteps * 1.31 + 4.5)   |   <= 256 tiles (4-stage ring form): ksteps * 0.72 + 4.5
-// Workspace: [1024 ticket counters, zero when handed over -- the kernel leaves them zero][tiles x S slabs of 256 KiB].
-constexpr long long INL_CNT_BYTES = 4096, INL_SLAB_BYTES = 256 * 256 * 4;
-struct NtPlan { int tile, slices; };
-
-NtPlan nt_plan(int M, int N, int K, int nb) {
-    static const int mode = [] { const char* e = getenv("ALM_GEMM_NT_INL"); return e ? atoi(e) : 1; }();     // 0: off (A/B), 1: cost model, >= 2: that many slices wherever they fit
-    const int base = pick_tile(M, N, nb, 0, false);
-    if (mode == 0 || base != 1 || M < 256 || N < 256) return NtPlan{base, 1};
-    const long long t256 = (long long)((M + 255) / 256) * ((N + 255) / 256) * nb;
-    const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128) * nb;
-    if (t256 > 128) return NtPlan{base, 1};                                     // (two slices must fit one resident round)
-    const int ksteps = (K + BK - 1) / BK;
-    double best_t = t128 <= 256 ? ksteps * 0.72 + 4.5 : (double)((t128 + 511) / 512) * (ksteps * 1.31 + 4.5);
-    NtPlan best{base, 1};
-    for (int S = 2; S <= 8; ++S) {
-        const long long W = t256 * S;
-        if (W > 256) break;
-        const int kc = (ksteps + S - 1) / S;
-        if (kc < 4) break;
-        if ((ksteps + kc - 1) / kc != S) continue;                              // (no empty slices)
-        const double t = kc * (1.15 + 0.0033 * W) + 7.0 + (8.0 + 0.04 * W) + 2.6 * (S == 2 ? 1 : S);
-        if (mode >= 2 ? (S == mode || best.slices == 1) : t < best_t) { best_t = t; best = NtPlan{13, S}; }
+    switch (tl) {
+    case 14: return out_f32 ? launch_w4<TNMODE, true>(p, ny, nz, st) : launch_w4<TNMODE, false>(p, ny, nz, st);
+    case 13: return out_f32 ? launch_stag<TNMODE, true>(p, ny, nz, st) : launch_stag<TNMODE, false>(p, ny, nz, st);
+    case 16: return out_f32 ? launch_ring<true>(p, ny, nz, st) : launch_ring<false>(p, ny, nz, st);
+    case 15: return out_f32 ? launch_cfg<256, 128, 4, 2, TNMODE, true>(p, ny, nz, st) : launch_cfg<256, 128, 4, 2, TNMODE, false>(p, ny, nz, st);
+    case 11: return out_f32 ? launch_cfg<384, 256, 2, 4, TNMODE, true>(p, ny, nz, st) : launch_cfg<384, 256, 2, 4, TNMODE, false>(p, ny, nz, st);
+    case 17: return out_f32 ? launch_cfg<320, 256, 2, 4, false, true>(p, ny, nz, st) : launch_cfg<320, 256, 2, 4, false, false>(p, ny, nz, st);
+    case 2: return out_f32 ? launch_cfg<256, 256, 2, 4, TNMODE, true>(p, ny, nz, st) : launch_cfg<256, 256, 2, 4, TNMODE, false>(p, ny, nz, st);
+    default: return out_f32 ? launch_cfg<128, 128, 2, 2, TNMODE, true>(p, ny, nz, st) : launch_cfg<128, 128, 2, 2, TNMODE, false>(p, ny, nz, st);
     }
-    return best;
 }
 
-// launch of one (possibly batched) NT problem on the plan above; p: as for launch_gemm<false>, raster 0, no split.  ws == nullptr or too small: the
+// launch of one (possibly batched) NT problem on nt_plan (gemm_plan.hpp); p: as for launch_gemm<false>, raster 0, no split.  ws == nullptr or too small: the
 // workspace-free choice of alm_gemm_bf16_nt
 int nt_launch_ws(const GemmParams& p0, int ny, int out_f32, int force_slices, void* ws, long long ws_bytes, hipStream_t st) {
     NtPlan pl = nt_plan(p0.M, p0.N, p0.K, ny);
+    const long long tiles = (long long)((p0.M + 255) / 256) * ((p0.N + 255) / 256) * ny;
     if (force_slices > 0) {
-        const long long t256 = (long long)((p0.M + 255) / 256) * ((p0.N + 255) / 256) * ny;
-        if (p0.M < 256 || p0.N < 256 || t256 > 1024) return ALM_ERR_UNSUPPORTED;
+        if (p0.M < 256 || p0.N < 256 || tiles > 1024) return ALM_ERR_UNSUPPORTED;
         pl = NtPlan{13, force_slices};
     }
     if (force_slices == 0 && (pl.tile != 13 || pl.slices < 2)) return launch_gemm<false>(p0, ny, 1, out_f32, 0, st);      // the workspace-free choice
-    const long long tiles = (long long)((p0.M + 255) / 256) * ((p0.N + 255) / 256) * ny;
     if (pl.slices == 1) return launch_gemm<false>(p0, ny, 1, out_f32, 13, st, false);      // (forced: the plain staggered tile)
     const long long need = INL_CNT_BYTES + tiles * pl.slices * INL_SLAB_BYTES;
     if (!ws || ws_bytes < need || ((uintptr_t)ws & 15)) {
@@ -1572,195 +1471,36 @@ int nt_launch_ws(const GemmParams& p0, int ny, int out_f32, int force_slices, vo
     if (p.inl_slices < 2) return launch_gemm<false>(p0, ny, 1, out_f32, 13, st, false);
     p.inl_cnt = reinterpret_cast<unsigned*>(ws);
     p.inl_ws = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(ws) + INL_CNT_BYTES);
-    p.group_m = pick_group(p, 13);
+    p.group_m = pick_group();
     return out_f32 ? launch_stag_inl<true>(p, ny, st) : launch_stag_inl<false>(p, ny, st);
-}
-
-// Split-K plan for `nb` same-shape problems: choose (tile, slices) minimising a simple time model --
-//   block waves over the chip x K-steps per block x measured time per K-step  +  workspace round trip through HBM.
-// (A balanced "stream-K"-like split -- one equally long K-step range per CU -- measured SLOWER: the workgroups of an XCD then walk different
-// K ranges and no longer share operand panels through the L2; it lives in csrc/lab/gemm_lab.hip)
-struct SplitPlan { int tile, slices; };
-
-// XCD-panel rasterisation pays only when the panels spread evenly over the 8 XCDs (measured: 22 panels +3 %, 11 panels -40 %)
-int pick_raster(int M, int N, int nb, int tile) {
-    const int bm = tile >= 2 ? 256 : 128;
-    const int tmm = (M + bm - 1) / bm, tnn = (N + bm - 1) / bm;
-    const int P = (tmm >= tnn ? tmm : tnn) * nb;
-    return (P % 8 == 0 || P >= 20) ? 1 : 0;
-}
-SplitPlan splitk_plan(int M, int N, int K, int nb) {
-    SplitPlan best{1, 1};
-    double best_t = 1e30;
-    for (int tile = 1; tile <= 2; ++tile) {
-        if (tile == 2 && (M < 256 || N < 256)) continue;
-        const int bm = tile == 2 ? 256 : 128;
-        const double tiles = (double)((M + bm - 1) / bm) * ((N + bm - 1) / bm) * nb;
-        const double slots = tile == 2 ? 256.0 : 512.0;               // resident blocks on the chip
-        const double us_per_kstep = tile == 2 ? 2.0 : 1.25;          // one 64-deep K-step of one block (measured, whole chip busy)
-        for (int s = 1; s <= 64; ++s) {
-            if (s > 1 && (K + s - 1) / s < 256) break;
-            const int kc = ((K + s - 1) / s + BK - 1) / BK * BK;
-            const int nsl = (K + kc - 1) / kc;
-            if (nsl != s) continue;
-            const double waves = ceil(tiles * s / slots);
-            double t = waves * ((kc / BK) * us_per_kstep + 3.0);
-            if (s > 1) t += (double)s * M * N * nb * 8.0 / 4.0e6 + 3.0;   // fp32 partials: written + read back at ~4 TB/s, + the reduce launch
-            if (t < best_t) { best_t = t; best = SplitPlan{tile == 2 ? 13 : 1, s}; }
-        }
-    }
-    return best;
-}
-
-// Hybrid plan of the layer-batched weight gradients (alm_gemm_bf16_tn_batched): when the 256 x 256 tiles of all problems fill the chip's 256 CUs a
-// whole number of times plus a SMALL remainder (dW1 of 3 layers: 264 tiles), the uniform split-K plan pays for the remainder with partials of
-// EVERYTHING (4 slices: 5 waves of K/4 + 270 MB of fp32 partials).  Instead: the first panels_a panels (whole waves) run at full K straight into C,
-// and the remaining row (column) blocks -- they all lie in the LAST problem -- are one ordinary split-K launch, sliced deep enough to occupy the chip
-// once.  panels_a == 0: not applicable (use the uniform plan).
-struct HybridPlan { int panels_a, m_major, off, slices_b; };
-HybridPlan hybrid_plan(int M, int N, int K, int nb) {
-    static const int off_switch = [] { const char* e = getenv("ALM_GEMM_HYBRID"); return e ? atoi(e) : 1; }();    // A/B switch (0: uniform plan)
-    HybridPlan none{0, 0, 0, 0};
-    if (!off_switch || M < 256 || N < 256 || K < 4096) return none;
-    const int tm = (M + 255) / 256, tn = (N + 255) / 256;
-    const int m_major = tm >= tn, tmaj = m_major ? tm : tn, Q = m_major ? tn : tm;
-    const int P = tmaj * nb, total = P * Q;
-    if (total <= 256) return none;
-    const int panels_a = (total / 256) * 256 / Q;                 // whole waves of 256 tiles (Q tiles per panel)
-    const int rem = P - panels_a;
-    if (panels_a * Q % 256 != 0 || rem <= 0 || rem >= tmaj || rem * Q > 64) return none;    // the tail must be small and inside the last problem
-    const int off = (tmaj - rem) * 256;
-    int s = 256 / (rem * Q);                                      // tail tiles x slices ~ one wave of the chip
-    const int ksteps = (K + BK - 1) / BK;
-    while (s > 1 && ksteps / s < 8) --s;                          // at least 8 K-steps per slice
-    if (s < 2) return none;
-    return HybridPlan{panels_a, m_major, off, s};
 }
 
 // one TN split-K problem with a GIVEN number of slices (the tail of the hybrid plan): partials into ws [slices][M][N], then the fixed-order reduce
 int splitk_fixed(const bf16_t* At, const bf16_t* Bt, float* C, float* ws, int M, int N, int K, long long lda, long long ldb, long long ldc, int slices,
                  float alpha, int accumulate, hipStream_t st) {
-    int kc = (K + slices - 1) / slices;
-    kc = (kc + BK - 1) / BK * BK;
-    const int nsl = (K + kc - 1) / kc;
+    const SplitGeometry g = split_geometry(K, slices);
     const long long mn = (long long)M * N;
-    GemmParams p{At, Bt, ws, nullptr, M, N, K, lda, ldb, (long long)N, 1, 0, 0, 0, 0, 0, mn, alpha, 0, kc, mn, 0, nsl, 1};
-    int rc = launch_gemm<true>(p, 1, nsl, 1, 13, st);
+    GemmParams p{At, Bt, ws, nullptr, M, N, K, lda, ldb, (long long)N, 1, 0, 0, 0, 0, 0, mn, alpha, 0, g.kc, mn, 0, g.nsl, 1};
+    int rc = launch_gemm<true>(p, 1, g.nsl, 1, 13, st);
     if (rc) return rc;
-    const int grid = (int)((mn + 255) / 256 < 2048 ? (mn + 255) / 256 : 2048);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid, 1), dim3(256), 0, st, (const float*)ws, nsl, mn, mn, N, C, ldc, 0LL, accumulate);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(reduce_grid(mn), 1), dim3(256), 0, st, (const float*)ws, g.nsl, mn, mn, N, C, ldc, 0LL, accumulate);
     return 0;
 }
 
 // step (a) of the hybrid plan: the first hy.panels_a panels (whole rounds of the chip) at full K, straight into C -- no partials, no reduce
-int hybrid_panels_launch(const void* At, const void* Bt, float* C, int M, int N, int K, long long lda, long long ldb, long long ldc, int nb1, int nb2, long long sA1,
-                         long long sA2, long long sB1, long long sB2, long long sC1, long long sC2, float alpha, int accumulate, const HybridPlan& hy, hipStream_t st) {
-    static const int raster_a = [] { const char* e = getenv("ALM_GEMM_HYBRID_RASTER"); return e ? atoi(e) : 2; }();    // A/B switch: 1 = round-robin panels
-    GemmParams pa{(const bf16_t*)At, (const bf16_t*)Bt, C, nullptr, M, N, K, lda, ldb, ldc, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, 0, 0,
-                  (hy.panels_a % 8 == 0 && raster_a == 2) ? 2 : 1, 1, nb1 * nb2, hy.panels_a};
-    return launch_gemm<true>(pa, nb1 * nb2, 1, 1, 13, st, true, true);
+int hybrid_panels_launch(const AlmTnJob& j, const HybridPlan& hy, hipStream_t st) {
+    GemmParams pa{(const bf16_t*)j.At, (const bf16_t*)j.Bt, j.C, nullptr, j.M, j.N, j.K, j.lda, j.ldb, j.ldc, j.nb2, j.sA1, j.sA2, j.sB1, j.sB2, j.sC1, j.sC2, j.alpha,
+                  j.accumulate, 0, 0, (hy.panels_a % 8 == 0 && gemm_env().hybrid_raster == 2) ? 2 : 1, 1, j.nb1 * j.nb2, hy.panels_a};
+    return launch_gemm<true>(pa, j.nb1 * j.nb2, 1, 1, 13, st, true, true);
 }
 
 // the tail of the hybrid plan as a problem of its own: the last problem's remaining row (column) blocks
-AlmTnJob hybrid_tail(const void* At, const void* Bt, float* C, int M, int N, int K, long long lda, long long ldb, long long ldc, int nb1, int nb2, long long sA1,
-                     long long sA2, long long sB1, long long sB2, long long sC1, long long sC2, float alpha, int accumulate, const HybridPlan& hy) {
-    const long long zA = (long long)(nb1 - 1) * sA1 + (long long)(nb2 - 1) * sA2, zB = (long long)(nb1 - 1) * sB1 + (long long)(nb2 - 1) * sB2;
-    const long long zC = (long long)(nb1 - 1) * sC1 + (long long)(nb2 - 1) * sC2;
-    return AlmTnJob{(const bf16_t*)At + zA + (hy.m_major ? hy.off : 0), (const bf16_t*)Bt + zB + (hy.m_major ? 0 : hy.off),
-                    C + zC + (hy.m_major ? (long long)hy.off * ldc : hy.off), hy.m_major ? M - hy.off : M, hy.m_major ? N : N - hy.off, K, 1, 1, accumulate, alpha, 0,
-                    lda, ldb, ldc, 0, 0, 0, 0, 0, 0};
-}
-
-// ---- plan of the grouped leftover launch (gemm_tn_grouped_kernel) ------------------------------------------------------------------------------------
-// ONE slice count S for all jobs, from a time model in the form of the measured NT one (docs/LABBOOK.md round 6, item 2: us = 9.0 + 1.52 ksteps + 18.1 (S > 1) + 2.6 S per
-// launch of one resident round), re-fitted to this launch at the headline's leftovers (144 tiles, K = 16384, S = 1 .. 10; docs/LABBOOK.md round 7):
-//   t(S) = full rounds x (TNG_ROUND_US + TNG_KSTEP_US x kps)  +  last, partial round: TNG_ROUND_US + kps x (TNG_KSTEP_LO_US + (TNG_KSTEP_US - TNG_KSTEP_LO_US) x f)
-//          +  [S > 1]  (TNG_PUBLISH_US + (S + 1) x leftover bytes / TNG_REDUCE_BPUS)
-// kps = K-steps per slice; rounds = the busiest XCD's workgroups / its 32 CUs, f = the filled fraction of the last one (a K-step of a 256 x 256 workgroup takes
-// 1.2 us on a nearly empty chip and 1.9 us on a full one: a part-filled last round is cheaper than a whole one).  Reproduces the ten measured totals to 7 %
-// and their order (S = 5 at the headline shape).  Slices are whole K-steps, none empty, at least 4 K-steps each.
-constexpr double TNG_ROUND_US = 9.0, TNG_KSTEP_US = 1.92, TNG_KSTEP_LO_US = 1.2, TNG_PUBLISH_US = 18.1, TNG_REDUCE_BPUS = 5.8e6;
-struct TnGroupPlan { int tiles, S, kps, pieces, blocks, rounds; long long ws_floats; int longest; };
-
-bool tn_job_live(const AlmTnJob& j) { return j.M > 0 && j.N > 0 && j.nb1 > 0 && j.nb2 > 0; }
-
-int tn_jobs_check(const AlmTnJob* jobs, int njobs) {
-    if (njobs < 0 || njobs > TN_GROUP_MAX || (njobs > 0 && !jobs)) return ALM_ERR_BAD_ARG;
-    int K = 0;
-    for (int i = 0; i < njobs; ++i) {
-        const AlmTnJob& j = jobs[i];
-        if (!tn_job_live(j)) continue;
-        if (j.K <= 0 || (K && j.K != K)) return ALM_ERR_BAD_ARG;            // one contraction length per call
-        K = j.K;
-        if ((j.lda & 7) || (j.ldb & 7) || ((j.sA1 | j.sA2 | j.sB1 | j.sB2) & 7) || ((uintptr_t)j.At & 15) || ((uintptr_t)j.Bt & 15)) return ALM_ERR_BAD_ARG;
-        if (view_too_big(j.K, j.lda) || view_too_big(j.K, j.ldb)) return ALM_ERR_UNSUPPORTED;
-        if ((long long)j.nb1 * j.nb2 > 4096 || j.M > (1 << 23) || j.N > (1 << 23)) return ALM_ERR_UNSUPPORTED;
-    }
-    return 0;
-}
-
-// geometry of the launch for a GIVEN S: fills tiles / pieces / blocks / rounds / ws_floats (and the table's placement arrays when tb != nullptr)
-void tn_group_geometry(const AlmTnJob* jobs, int njobs, int S, TnGroupPlan* pl, TnGroupTable* tb) {
-    int base = 0, nj = 0, tiles = 0;
-    int b_[TN_GROUP_MAX], n_[TN_GROUP_MAX], t_[TN_GROUP_MAX];
-    long long wsf = 0;
-    for (int i = 0; i < njobs; ++i) {
-        const AlmTnJob& j = jobs[i];
-        if (!tn_job_live(j)) continue;
-        const int tm = (j.M + 255) / 256, tn = (j.N + 255) / 256, nbt = j.nb1 * j.nb2;
-        b_[nj] = base; n_[nj] = nbt * S; t_[nj] = tm * tn;
-        if (tb) { tb->tiles[nj] = tm * tn; tb->tiles_n[nj] = tn; tb->nunits[nj] = nbt * S; tb->base[nj] = base; }
-        base += nbt * S;
-        tiles += tm * tn * nbt;
-        if (S > 1) wsf += ((long long)S * nbt * j.M * j.N + 3) & ~3LL;      // (every job's partials start 16-byte aligned)
-        ++nj;
-    }
-    int longest = 0;
-    for (int x = 0; x < 8; ++x) {
-        int len = 0, first;
-        for (int k = 0; k < nj; ++k) len += tn_group_units_on(b_[k], n_[k], x, &first) * t_[k];
-        longest = len > longest ? len : longest;
-    }
-    pl->tiles = tiles; pl->S = S; pl->pieces = tiles * S; pl->blocks = 8 * longest; pl->rounds = (longest + 31) / 32; pl->ws_floats = wsf; pl->longest = longest;
-    if (tb) { tb->njobs = nj; tb->S = S; }
-}
-
-// K-steps per slice when K is cut into S slices of whole K-steps, or 0 when that leaves a slice empty
-int tn_group_kps(int K, int S) {
-    const int ksteps = (K + BK - 1) / BK, kps = (ksteps + S - 1) / S;
-    return (ksteps + kps - 1) / kps == S ? kps : 0;
-}
-
-TnGroupPlan tn_group_plan(const AlmTnJob* jobs, int njobs, int slices) {
-    TnGroupPlan best{0, 1, 0, 0, 0, 0, 0, 0};
-    int K = 0;
-    double elems = 0.;
-    for (int i = 0; i < njobs; ++i)
-        if (tn_job_live(jobs[i])) { K = jobs[i].K; elems += (double)jobs[i].nb1 * jobs[i].nb2 * jobs[i].M * jobs[i].N; }
-    if (K == 0) return best;
-    if (slices > 0) {                                                       // forced: the nearest count at or below it that leaves no slice empty
-        int S = slices;
-        while (S > 1 && tn_group_kps(K, S) == 0) --S;
-        tn_group_geometry(jobs, njobs, S, &best, nullptr);
-        best.kps = tn_group_kps(K, S);
-        return best;
-    }
-    double best_t = 1e30;
-    for (int S = 1; S <= 32; ++S) {
-        const int kps = tn_group_kps(K, S);
-        if (kps == 0 || (S > 1 && kps < 4)) continue;
-        TnGroupPlan pl;
-        tn_group_geometry(jobs, njobs, S, &pl, nullptr);
-        pl.kps = kps;
-        if (pl.ws_floats > 0x7fffffffLL) break;
-        const int full = pl.longest / 32;
-        const double f = (pl.longest % 32) / 32.0;
-        double t = full * (TNG_ROUND_US + TNG_KSTEP_US * kps);
-        if (f > 0.) t += TNG_ROUND_US + kps * (TNG_KSTEP_LO_US + (TNG_KSTEP_US - TNG_KSTEP_LO_US) * f);
-        if (S > 1) t += TNG_PUBLISH_US + (S + 1) * elems * 4.0 / TNG_REDUCE_BPUS;
-        if (t < best_t) { best_t = t; best = pl; }
-    }
-    return best;
+AlmTnJob hybrid_tail(const AlmTnJob& j, const HybridPlan& hy) {
+    const long long zA = (long long)(j.nb1 - 1) * j.sA1 + (long long)(j.nb2 - 1) * j.sA2, zB = (long long)(j.nb1 - 1) * j.sB1 + (long long)(j.nb2 - 1) * j.sB2;
+    const long long zC = (long long)(j.nb1 - 1) * j.sC1 + (long long)(j.nb2 - 1) * j.sC2;
+    return AlmTnJob{(const bf16_t*)j.At + zA + (hy.m_major ? hy.off : 0), (const bf16_t*)j.Bt + zB + (hy.m_major ? 0 : hy.off),
+                    j.C + zC + (hy.m_major ? (long long)hy.off * j.ldc : hy.off), hy.m_major ? j.M - hy.off : j.M, hy.m_major ? j.N : j.N - hy.off, j.K, 1, 1,
+                    j.accumulate, j.alpha, 0, j.lda, j.ldb, j.ldc, 0, 0, 0, 0, 0, 0};
 }
 
 }  // namespace
@@ -1769,33 +1509,21 @@ extern "C" int alm_gemm_bf16_nt(const void* A, const void* B, void* C, const flo
                                 long long ldb, long long ldc, int nb1, int nb2, long long sA1, long long sA2, long long sB1,
                                 long long sB2, long long sC1, long long sC2, float alpha, int out_f32, int accumulate, void* stream) {
     if (M <= 0 || N <= 0 || nb1 <= 0 || nb2 <= 0) return 0;
-    if (K <= 0 || (K & 7) || (lda & 7) || (ldb & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return ALM_ERR_BAD_ARG;
-    if (((sA1 | sA2 | sB1 | sB2) & 7) != 0) return ALM_ERR_BAD_ARG;
-    if (view_too_big(384, lda) || view_too_big(256, ldb)) return ALM_ERR_UNSUPPORTED;
+    if (const int rc = nt_operands_ok(A, B, K, lda, ldb, sA1 | sA2 | sB1 | sB2, 384, 256)) return rc;
     GemmParams p{(const bf16_t*)A, (const bf16_t*)B, C, bias, M, N, K, lda, ldb, ldc, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, 0, 0, 0, 1};
-    int rc = launch_gemm<false>(p, nb1 * nb2, 1, out_f32, 0, (hipStream_t)stream);
-    if (rc) return rc;
-    ALM_LAUNCH_CHECK();
-    return 0;
+    return checked(launch_gemm<false>(p, nb1 * nb2, 1, out_f32, 0, (hipStream_t)stream));
 }
 
-// alm_gemm_bf16_nt with a caller-owned workspace (round 6): launches that leave most of the chip idle on 256 x 256 tiles (< 192 of them: every D- / 512-wide
-// projection at M = 8192, to_q / dAO at M = 16384) run on the staggered tile with IN-LAUNCH split-K when the measured cost model says so (nt_plan): each K
-// slice publishes its fp32 accumulators to `ws`, the tile's last arriver reduces them in fixed slice order and runs the usual epilogue -- bitwise
-// deterministic, no second launch, no atomics on data.  ws: >= alm_gemm_nt_ws_bytes() bytes, 16-byte aligned, its first 4096 bytes ZERO when first handed
-// over (ticket counters; every launch leaves them zero), used by ONE stream at a time.  ws == NULL (or too small): exactly alm_gemm_bf16_nt.
+// alm_gemm_bf16_nt with a caller-owned workspace (round 6; contract of `ws`: include/audiolm_hip.h): launches that leave most of the chip idle on 256 x 256
+// tiles run on the staggered tile with IN-LAUNCH split-K when the measured cost model says so (nt_plan in gemm_plan.hpp) -- bitwise deterministic, no second
+// launch, no atomics on data.  ws == NULL (or too small): exactly alm_gemm_bf16_nt.
 extern "C" int alm_gemm_bf16_nt_ws(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long long lda, long long ldb, long long ldc,
                                    int nb1, int nb2, long long sA1, long long sA2, long long sB1, long long sB2, long long sC1, long long sC2, float alpha,
                                    int out_f32, int accumulate, void* ws, long long ws_bytes, void* stream) {
     if (M <= 0 || N <= 0 || nb1 <= 0 || nb2 <= 0) return 0;
-    if (K <= 0 || (K & 7) || (lda & 7) || (ldb & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return ALM_ERR_BAD_ARG;
-    if (((sA1 | sA2 | sB1 | sB2) & 7) != 0) return ALM_ERR_BAD_ARG;
-    if (view_too_big(384, lda) || view_too_big(256, ldb)) return ALM_ERR_UNSUPPORTED;
+    if (const int rc = nt_operands_ok(A, B, K, lda, ldb, sA1 | sA2 | sB1 | sB2, 384, 256)) return rc;
     GemmParams p{(const bf16_t*)A, (const bf16_t*)B, C, bias, M, N, K, lda, ldb, ldc, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, 0, 0, 0, 1};
-    int rc = nt_launch_ws(p, nb1 * nb2, out_f32, 0, ws, ws_bytes, (hipStream_t)stream);
-    if (rc) return rc;
-    ALM_LAUNCH_CHECK();
-    return 0;
+    return checked(nt_launch_ws(p, nb1 * nb2, out_f32, 0, ws, ws_bytes, (hipStream_t)stream));
 }
 
 // the same with a GIVEN number of K slices on the staggered 256 x 256 tile, un-batched (tests / the cost-model benchmark scripts/ab_nt_inl.py); slices = 1: the
@@ -1803,31 +1531,17 @@ extern "C" int alm_gemm_bf16_nt_ws(const void* A, const void* B, void* C, const 
 extern "C" int alm_gemm_bf16_nt_inl(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long long lda, long long ldb, long long ldc,
                                     float alpha, int out_f32, int accumulate, int slices, void* ws, long long ws_bytes, void* stream) {
     if (M <= 0 || N <= 0) return 0;
-    if (K <= 0 || (K & 7) || (lda & 7) || (ldb & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || slices < 1 || slices > 16) return ALM_ERR_BAD_ARG;
-    if (view_too_big(384, lda) || view_too_big(256, ldb)) return ALM_ERR_UNSUPPORTED;
+    if (slices < 1 || slices > 16) return ALM_ERR_BAD_ARG;
+    if (const int rc = nt_operands_ok(A, B, K, lda, ldb, 0, 384, 256)) return rc;
     GemmParams p{(const bf16_t*)A, (const bf16_t*)B, C, bias, M, N, K, lda, ldb, ldc, 1, 0, 0, 0, 0, 0, 0, alpha, accumulate, 0, 0, 0, 1};
-    int rc = nt_launch_ws(p, 1, out_f32, slices, ws, ws_bytes, (hipStream_t)stream);
-    if (rc) return rc;
-    ALM_LAUNCH_CHECK();
-    return 0;
+    return checked(nt_launch_ws(p, 1, out_f32, slices, ws, ws_bytes, (hipStream_t)stream));
 }
 
 // Host-side plan query of alm_gemm_bf16_nt_ws (no launch, no GPU): plan[0] = block tile (1 = 128 x 128, 16 = its 4-stage DMA-ring form, 13 = 256 x 256 staggered,
 // 11 = 384 x 256), plan[1] = K slices of the in-launch split-K form (1: none), plan[2] = workspace bytes that plan needs (0: none), plan[3] = workgroups
 extern "C" int alm_gemm_nt_plan(int M, int N, int K, int nb, int with_ws, int* plan) {
-    nb = nb < 1 ? 1 : nb;
-    NtPlan pl = with_ws ? nt_plan(M, N, K, nb) : NtPlan{pick_tile(M, N, nb, 0, false), 1};
-    int tile = pl.tile;
-    const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128) * nb;
-    static const int ring_on = [] { const char* e = getenv("ALM_GEMM_RING"); return e ? atoi(e) : 1; }();
-    if (tile == 1 && ring_on && K >= 256 && t128 <= 256) tile = 16;
-    const long long bm = tile == 11 ? 384 : (tile == 17 ? 320 : (tile == 13 ? 256 : 128)), bn = tile == 1 || tile == 16 ? 128 : 256;
-    const long long wgs = ((M + bm - 1) / bm) * ((N + bn - 1) / bn) * nb * pl.slices;
-    if (plan) {
-        plan[0] = tile; plan[1] = pl.slices;
-        plan[2] = pl.slices > 1 ? (int)(INL_CNT_BYTES + (wgs * INL_SLAB_BYTES)) : 0;
-        plan[3] = (int)wgs;
-    }
+    const NtQuery q = nt_query(M, N, K, nb < 1 ? 1 : nb, with_ws != 0);
+    if (plan) { plan[0] = q.tile; plan[1] = q.slices; plan[2] = (int)q.ws_bytes; plan[3] = (int)q.wgs; }
     return 0;
 }
 
@@ -1841,59 +1555,41 @@ extern "C" int alm_gemm_nt_ws_bytes(void) { return (int)(INL_CNT_BYTES + 256 * I
 extern "C" int alm_gemm_bf16_nt_group2(const void* A0, const void* B0, void* C0, int M0, int N0, int K0, long long lda0, long long ldb0, long long ldc0,
                                        const void* A1, const void* B1, void* C1, int M1, int N1, int K1, long long lda1, long long ldb1, long long ldc1,
                                        int out_f32, void* stream) {
-    static const int on = [] { const char* e = getenv("ALM_GEMM_GROUP2"); return e ? atoi(e) : 1; }();
+    const GemmEnv& env = gemm_env();
     hipStream_t st = (hipStream_t)stream;
-    auto bad = [](const void* A, const void* B, int K, long long lda, long long ldb) {
-        return K <= 0 || (K & 7) || (lda & 7) || (ldb & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15);
+    const auto one_by_one = [&] {
+        const int rc = alm_gemm_bf16_nt(A0, B0, C0, nullptr, M0, N0, K0, lda0, ldb0, ldc0, 1, 1, 0, 0, 0, 0, 0, 0, 1.f, out_f32, 0, stream);
+        return rc ? rc : alm_gemm_bf16_nt(A1, B1, C1, nullptr, M1, N1, K1, lda1, ldb1, ldc1, 1, 1, 0, 0, 0, 0, 0, 0, 1.f, out_f32, 0, stream);
     };
-    if (M0 <= 0 || N0 <= 0 || M1 <= 0 || N1 <= 0) {
-        int rc = alm_gemm_bf16_nt(A0, B0, C0, nullptr, M0, N0, K0, lda0, ldb0, ldc0, 1, 1, 0, 0, 0, 0, 0, 0, 1.f, out_f32, 0, stream);
-        if (rc) return rc;
-        return alm_gemm_bf16_nt(A1, B1, C1, nullptr, M1, N1, K1, lda1, ldb1, ldc1, 1, 1, 0, 0, 0, 0, 0, 0, 1.f, out_f32, 0, stream);
-    }
-    if (bad(A0, B0, K0, lda0, ldb0) || bad(A1, B1, K1, lda1, ldb1)) return ALM_ERR_BAD_ARG;
-    if (view_too_big(384, lda0) || view_too_big(256, ldb0) || view_too_big(384, lda1) || view_too_big(256, ldb1)) return ALM_ERR_UNSUPPORTED;
+    if (M0 <= 0 || N0 <= 0 || M1 <= 0 || N1 <= 0) return one_by_one();
+    const int e0 = nt_operands_ok(A0, B0, K0, lda0, ldb0, 0, 384, 256), e1 = nt_operands_ok(A1, B1, K1, lda1, ldb1, 0, 384, 256);
+    if (e0 || e1) return e0 == ALM_ERR_BAD_ARG || e1 == ALM_ERR_BAD_ARG ? ALM_ERR_BAD_ARG : ALM_ERR_UNSUPPORTED;        // (a bad argument of either comes first)
     int t0 = pick_tile(M0, N0, 1, 0, false), t1 = pick_tile(M1, N1, 1, 0, false);
-    // round 6, measured and NOT adopted (switch kept for A/B runs, default off): two problems that are each too small for the big tile (< 192 tiles of
-    // 256 x 256) but TOGETHER fill the chip in one round on the staggered tile (dXN_q || dX_kv at M = 8192: 128 + 128 tiles) -- 23.1 us against 22.3 us on
-    // the 128 x 128 tile (profiles/r6b_group2.log): K = 512 / 128 is 8 / 2 K-steps, the staggered tile's fill + drain dominates
-    static const int grp_big = [] { const char* e = getenv("ALM_GEMM_GROUP2_BIG"); return e ? atoi(e) : 0; }();
-    if (grp_big && t0 == 1 && t1 == 1 && M0 >= 256 && N0 >= 256 && M1 >= 256 && N1 >= 256) {
+    if (env.group2_big && t0 == 1 && t1 == 1 && M0 >= 256 && N0 >= 256 && M1 >= 256 && N1 >= 256) {
         const long long a = (long long)((M0 + 255) / 256) * ((N0 + 255) / 256), b = (long long)((M1 + 255) / 256) * ((N1 + 255) / 256);
         if (a + b >= 192 && a + b <= 256 && (a & 7) == 0) t0 = t1 = 13;
     }
     const int bm = t0 == 1 ? 128 : 256;
     const int tiles0 = ((M0 + bm - 1) / bm) * ((N0 + bm - 1) / bm), tiles1 = ((M1 + bm - 1) / bm) * ((N1 + bm - 1) / bm);
-    if (!on || t0 != t1 || (t0 != 1 && t0 != 13) || (tiles0 & 7)) {
-        int rc = alm_gemm_bf16_nt(A0, B0, C0, nullptr, M0, N0, K0, lda0, ldb0, ldc0, 1, 1, 0, 0, 0, 0, 0, 0, 1.f, out_f32, 0, stream);
-        if (rc) return rc;
-        return alm_gemm_bf16_nt(A1, B1, C1, nullptr, M1, N1, K1, lda1, ldb1, ldc1, 1, 1, 0, 0, 0, 0, 0, 0, 1.f, out_f32, 0, stream);
-    }
+    if (!env.group2 || t0 != t1 || (t0 != 1 && t0 != 13) || (tiles0 & 7)) return one_by_one();
     GemmParams p0{(const bf16_t*)A0, (const bf16_t*)B0, C0, nullptr, M0, N0, K0, lda0, ldb0, ldc0, 1, 0, 0, 0, 0, 0, 0, 1.f, 0, 0, 0, 0, 1};
     GemmParams p1{(const bf16_t*)A1, (const bf16_t*)B1, C1, nullptr, M1, N1, K1, lda1, ldb1, ldc1, 1, 0, 0, 0, 0, 0, 0, 1.f, 0, 0, 0, 0, 1};
-    p0.group_m = pick_group(p0, t0);
-    p1.group_m = pick_group(p1, t1);
+    p0.group_m = p1.group_m = pick_group();
     auto launch = [&](auto kfn, int threads, int smem) -> int { return alm_launch_lds(kfn, dim3(tiles0 + tiles1), dim3(threads), smem, st, p0, p1, tiles0); };
     int rc;
     if (t0 == 1) rc = out_f32 ? launch(gemm_group2_kernel<128, 128, 2, 2, false, true>, 256, 2 * (128 + 128) * BK * 2)
                               : launch(gemm_group2_kernel<128, 128, 2, 2, false, false>, 256, 2 * (128 + 128) * BK * 2);
     else rc = out_f32 ? launch(gemm_stag_group2_kernel<false, true>, 512, 163840) : launch(gemm_stag_group2_kernel<false, false>, 512, 163840);
-    if (rc) return rc;
-    ALM_LAUNCH_CHECK();
-    return 0;
+    return checked(rc);
 }
 
 /* tile-selectable form of the above without batching (tests / benchmarks): see pick_tile for the ids */
 extern "C" int alm_gemm_bf16_nt_tile(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long long lda,
                                      long long ldb, long long ldc, float alpha, int out_f32, int accumulate, int tile, void* stream) {
     if (M <= 0 || N <= 0) return 0;
-    if (K <= 0 || (K & 7) || (lda & 7) || (ldb & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return ALM_ERR_BAD_ARG;
-    if (view_too_big(384, lda) || view_too_big(256, ldb)) return ALM_ERR_UNSUPPORTED;
+    if (const int rc = nt_operands_ok(A, B, K, lda, ldb, 0, 384, 256)) return rc;
     GemmParams p{(const bf16_t*)A, (const bf16_t*)B, C, bias, M, N, K, lda, ldb, ldc, 1, 0, 0, 0, 0, 0, 0, alpha, accumulate, 0, 0, 0, 1};
-    int rc = launch_gemm<false>(p, 1, 1, out_f32, tile, (hipStream_t)stream, false);
-    if (rc) return rc;
-    ALM_LAUNCH_CHECK();
-    return 0;
+    return checked(launch_gemm<false>(p, 1, 1, out_f32, tile, (hipStream_t)stream, false));
 }
 
 // Split-K for long-K / few-tile contractions (weight gradients: K = B*N tokens), `nb` same-shape problems per launch (element
@@ -1928,49 +1624,34 @@ extern "C" int alm_gemm_tn_batched_plan(int M, int N, int K, int nb, int* plan) 
 
 // fp32 workspace floats alm_gemm_bf16_{nt,tn}_splitk need for this problem (0: none)
 extern "C" int alm_gemm_splitk_ws_floats(int M, int N, int K, int nb) {
-    nb = nb < 1 ? 1 : nb;
-    const SplitPlan pl = splitk_plan(M, N, K, nb);
-    long long fl = pl.slices > 1 ? (long long)pl.slices * nb * M * N : 0;
-    const HybridPlan hy = hybrid_plan(M, N, K, nb);               // alm_gemm_bf16_tn_batched: the tail's partials (the larger of the two covers both callers)
-    if (hy.panels_a > 0) {
-        const long long m2 = hy.m_major ? M - hy.off : M, n2 = hy.m_major ? N : N - hy.off;
-        const long long f2 = (long long)hy.slices_b * m2 * n2;
-        if (f2 > fl) fl = f2;
-    }
+    const long long fl = splitk_ws_floats(M, N, K, nb < 1 ? 1 : nb);
     return fl > 0x7fffffffLL ? -1 : (int)fl;
 }
 
-static int splitk_common(bool tn, const void* A, const void* B, float* C, float* ws, int M, int N, int K, long long lda, long long ldb,
-                         long long ldc, int nb, long long sA, long long sB, long long sC, float alpha, int accumulate, hipStream_t st) {
+// the uniform plan (splitk_plan) of nb1 x nb2 same-shape problems: one launch at full K, or K slices into ws [slice][nb1][nb2][M][N] + the fixed-order reduce
+// (the one-level entry points: nb1 = 1, the first-level strides 0)
+static int splitk_uniform(bool tn, const void* A, const void* B, float* C, float* ws, int M, int N, int K, long long lda, long long ldb, long long ldc, int nb1, int nb2,
+                          long long sA1, long long sA2, long long sB1, long long sB2, long long sC1, long long sC2, float alpha, int accumulate, hipStream_t st) {
+    const int nb = nb1 * nb2;
     const SplitPlan pl = splitk_plan(M, N, K, nb);
-    if (pl.slices <= 1) {
-        GemmParams p{(const bf16_t*)A, (const bf16_t*)B, C, nullptr, M, N, K, lda, ldb, ldc, nb, 0, sA, 0, sB, 0, sC, alpha, accumulate, 0, 0, pick_raster(M, N, nb, pl.tile), 1};
-        return tn ? launch_gemm<true>(p, nb, 1, 1, pl.tile, st) : launch_gemm<false>(p, nb, 1, 1, pl.tile, st);
-    }
-    if (!ws) return ALM_ERR_BAD_ARG;
-    int kc = (K + pl.slices - 1) / pl.slices;
-    kc = (kc + BK - 1) / BK * BK;
-    const int nsl = (K + kc - 1) / kc;
+    if (pl.slices > 1 && !ws) return ALM_ERR_BAD_ARG;
+    const SplitGeometry g = pl.slices > 1 ? split_geometry(K, pl.slices) : SplitGeometry{0, 1};
     const long long mn = (long long)M * N;
-    GemmParams p{(const bf16_t*)A, (const bf16_t*)B, ws, nullptr, M, N, K, lda, ldb, (long long)N, nb, 0, sA, 0, sB, 0, mn, alpha, 0, kc, mn * nb, pick_raster(M, N, nb, pl.tile), nsl};
-    int rc = tn ? launch_gemm<true>(p, nb, nsl, 1, pl.tile, st) : launch_gemm<false>(p, nb, nsl, 1, pl.tile, st);
-    if (rc) return rc;
-    const int grid = (int)((mn + 255) / 256 < 2048 ? (mn + 255) / 256 : 2048);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid, nb), dim3(256), 0, st, (const float*)ws, nsl, mn, mn * nb, N, C, ldc, sC, accumulate);
-    return 0;
+    GemmParams p{(const bf16_t*)A, (const bf16_t*)B, C, nullptr, M, N, K, lda, ldb, ldc, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, 0, 0,
+                 pick_raster(M, N, nb, pl.tile), 1, nb};
+    if (pl.slices > 1) { p.C = ws; p.ldc = N; p.sC1 = mn * nb2; p.sC2 = mn; p.accumulate = 0; p.ksplit = g.kc; p.sCk = mn * nb; p.nsl = g.nsl; }    // partials
+    const int rc = tn ? launch_gemm<true>(p, nb, g.nsl, 1, pl.tile, st) : launch_gemm<false>(p, nb, g.nsl, 1, pl.tile, st);
+    if (rc == 0 && pl.slices > 1)
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(reduce_grid(mn), nb), dim3(256), 0, st, (const float*)ws, g.nsl, mn, mn * nb, N, C, ldc, sC2, accumulate, nb2, sC1);
+    return rc;
 }
-
 
 extern "C" int alm_gemm_bf16_nt_splitk(const void* A, const void* B, float* C, float* ws, int M, int N, int K, long long lda, long long ldb,
                                        long long ldc, int nb, long long sA, long long sB, long long sC, float alpha, int accumulate,
                                        void* stream) {
     if (M <= 0 || N <= 0 || nb <= 0) return 0;
-    if (K <= 0 || (K & 7) || (lda & 7) || (ldb & 7) || ((sA | sB) & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return ALM_ERR_BAD_ARG;
-    if (view_too_big(256, lda) || view_too_big(256, ldb)) return ALM_ERR_UNSUPPORTED;
-    int rc = splitk_common(false, A, B, C, ws, M, N, K, lda, ldb, ldc, nb, sA, sB, sC, alpha, accumulate, (hipStream_t)stream);
-    if (rc) return rc;
-    ALM_LAUNCH_CHECK();
-    return 0;
+    if (const int rc = nt_operands_ok(A, B, K, lda, ldb, sA | sB, 256, 256)) return rc;
+    return checked(splitk_uniform(false, A, B, C, ws, M, N, K, lda, ldb, ldc, 1, nb, 0, sA, 0, sB, 0, sC, alpha, accumulate, (hipStream_t)stream));
 }
 
 // Weight-gradient form: C[M,N] fp32 (+)= alpha * sum_k At[k][m] * Bt[k][n]  (At: [K][lda], Bt: [K][ldb], row-major activations).
@@ -1978,12 +1659,8 @@ extern "C" int alm_gemm_bf16_tn_splitk(const void* At, const void* Bt, float* C,
                                        long long ldb, long long ldc, int nb, long long sA, long long sB, long long sC, float alpha,
                                        int accumulate, void* stream) {
     if (M <= 0 || N <= 0 || nb <= 0) return 0;
-    if (K <= 0 || (lda & 7) || (ldb & 7) || ((sA | sB) & 7) || ((uintptr_t)At & 15) || ((uintptr_t)Bt & 15)) return ALM_ERR_BAD_ARG;
-    if (view_too_big(K, lda) || view_too_big(K, ldb)) return ALM_ERR_UNSUPPORTED;
-    int rc = splitk_common(true, At, Bt, C, ws, M, N, K, lda, ldb, ldc, nb, sA, sB, sC, alpha, accumulate, (hipStream_t)stream);
-    if (rc) return rc;
-    ALM_LAUNCH_CHECK();
-    return 0;
+    if (const int rc = tn_operands_ok(At, Bt, K, lda, ldb, sA | sB)) return rc;
+    return checked(splitk_uniform(true, At, Bt, C, ws, M, N, K, lda, ldb, ldc, 1, nb, 0, sA, 0, sB, 0, sC, alpha, accumulate, (hipStream_t)stream));
 }
 
 // Two-level batched weight gradients (round 3): C[z1][z2][M][N] fp32 (+)= alpha * At[z1][z2][K][M]^T . Bt[z1][z2][K][N] for nb1 x nb2 same-shape problems
@@ -1994,45 +1671,17 @@ extern "C" int alm_gemm_bf16_tn_batched(const void* At, const void* Bt, float* C
                                         long long ldc, int nb1, int nb2, long long sA1, long long sA2, long long sB1, long long sB2, long long sC1,
                                         long long sC2, float alpha, int accumulate, void* stream) {
     if (M <= 0 || N <= 0 || nb1 <= 0 || nb2 <= 0) return 0;
-    if (K <= 0 || (lda & 7) || (ldb & 7) || ((sA1 | sA2 | sB1 | sB2) & 7) || ((uintptr_t)At & 15) || ((uintptr_t)Bt & 15)) return ALM_ERR_BAD_ARG;
-    if (view_too_big(K, lda) || view_too_big(K, ldb)) return ALM_ERR_UNSUPPORTED;
+    if (const int rc = tn_operands_ok(At, Bt, K, lda, ldb, sA1 | sA2 | sB1 | sB2)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int nb = nb1 * nb2;
-    const SplitPlan pl = splitk_plan(M, N, K, nb);
-    int rc;
-    const HybridPlan hy = hybrid_plan(M, N, K, nb);
-    if (hy.panels_a > 0) {
-        // (a) the panels that fill whole waves of the chip: full K, straight into C -- no partials, no reduce
-        rc = hybrid_panels_launch(At, Bt, C, M, N, K, lda, ldb, ldc, nb1, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, hy, st);
-        if (rc) return rc;
-        // (b) the last problem's remaining row (column) blocks: an ordinary split-K problem on the sub-matrix, deep enough to fill the chip once
-        const AlmTnJob t = hybrid_tail(At, Bt, C, M, N, K, lda, ldb, ldc, nb1, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, hy);
-        if (!ws) return ALM_ERR_BAD_ARG;
-        rc = splitk_fixed((const bf16_t*)t.At, (const bf16_t*)t.Bt, t.C, ws, t.M, t.N, K, lda, ldb, ldc, hy.slices_b, alpha, accumulate, st);
-        if (rc) return rc;
-        ALM_LAUNCH_CHECK();
-        return 0;
-    }
-    if (pl.slices <= 1) {
-        GemmParams p{(const bf16_t*)At, (const bf16_t*)Bt, C, nullptr, M, N, K, lda, ldb, ldc, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, 0, 0,
-                     pick_raster(M, N, nb, pl.tile), 1, nb};
-        rc = launch_gemm<true>(p, nb, 1, 1, pl.tile, st);
-    } else {
-        if (!ws) return ALM_ERR_BAD_ARG;
-        int kc = (K + pl.slices - 1) / pl.slices;
-        kc = (kc + BK - 1) / BK * BK;
-        const int nsl = (K + kc - 1) / kc;
-        const long long mn = (long long)M * N;
-        GemmParams p{(const bf16_t*)At, (const bf16_t*)Bt, ws, nullptr, M, N, K, lda, ldb, (long long)N, nb2, sA1, sA2, sB1, sB2, mn * nb2, mn, alpha, 0, kc, mn * nb,
-                     pick_raster(M, N, nb, pl.tile), nsl, nb};
-        rc = launch_gemm<true>(p, nb, nsl, 1, pl.tile, st);
-        if (rc) return rc;
-        const int grid = (int)((mn + 255) / 256 < 2048 ? (mn + 255) / 256 : 2048);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid, nb), dim3(256), 0, st, (const float*)ws, nsl, mn, mn * nb, N, C, ldc, sC2, accumulate, nb2, sC1);
-    }
-    if (rc) return rc;
-    ALM_LAUNCH_CHECK();
-    return 0;
+    const HybridPlan hy = hybrid_plan(M, N, K, nb1 * nb2);
+    if (hy.panels_a <= 0) return checked(splitk_uniform(true, At, Bt, C, ws, M, N, K, lda, ldb, ldc, nb1, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, st));
+    // (a) the panels that fill whole waves of the chip: full K, straight into C -- no partials, no reduce
+    const AlmTnJob all{At, Bt, C, M, N, K, nb1, nb2, accumulate, alpha, 0, lda, ldb, ldc, sA1, sA2, sB1, sB2, sC1, sC2};
+    if (const int rc = hybrid_panels_launch(all, hy, st)) return rc;
+    // (b) the last problem's remaining row (column) blocks: an ordinary split-K problem on the sub-matrix, deep enough to fill the chip once
+    const AlmTnJob t = hybrid_tail(all, hy);
+    if (!ws) return ALM_ERR_BAD_ARG;
+    return checked(splitk_fixed((const bf16_t*)t.At, (const bf16_t*)t.Bt, t.C, ws, t.M, t.N, K, lda, ldb, ldc, hy.slices_b, alpha, accumulate, st));
 }
 
 // Step (a) of the hybrid plan above ALONE (the whole-round panels at full K, the same launch: the same bits in those C tiles); what is left -- the same tail
@@ -2044,15 +1693,13 @@ extern "C" int alm_gemm_bf16_tn_batched_panels(const void* At, const void* Bt, f
     if (!rest) return ALM_ERR_BAD_ARG;
     *rest = AlmTnJob{At, Bt, C, M, N, K, nb1, nb2, accumulate, alpha, 0, lda, ldb, ldc, sA1, sA2, sB1, sB2, sC1, sC2};
     if (M <= 0 || N <= 0 || nb1 <= 0 || nb2 <= 0) { rest->M = 0; return 0; }
-    if (K <= 0 || (lda & 7) || (ldb & 7) || ((sA1 | sA2 | sB1 | sB2) & 7) || ((uintptr_t)At & 15) || ((uintptr_t)Bt & 15)) return ALM_ERR_BAD_ARG;
-    if (view_too_big(K, lda) || view_too_big(K, ldb)) return ALM_ERR_UNSUPPORTED;
+    if (const int rc = tn_operands_ok(At, Bt, K, lda, ldb, sA1 | sA2 | sB1 | sB2)) return rc;
     const HybridPlan hy = hybrid_plan(M, N, K, nb1 * nb2);
     if (hy.panels_a <= 0) return 0;                                         // no whole round: everything is left
-    const int rc = hybrid_panels_launch(At, Bt, C, M, N, K, lda, ldb, ldc, nb1, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, hy, (hipStream_t)stream);
-    if (rc) return rc;
-    *rest = hybrid_tail(At, Bt, C, M, N, K, lda, ldb, ldc, nb1, nb2, sA1, sA2, sB1, sB2, sC1, sC2, alpha, accumulate, hy);
-    ALM_LAUNCH_CHECK();
-    return 0;
+    const AlmTnJob all = *rest;
+    if (const int rc = hybrid_panels_launch(all, hy, (hipStream_t)stream)) return rc;
+    *rest = hybrid_tail(all, hy);
+    return checked(0);
 }
 
 extern "C" int alm_gemm_tn_grouped_plan(const AlmTnJob* jobs, int njobs, int slices, int* plan) {
@@ -2079,7 +1726,10 @@ extern "C" int alm_gemm_bf16_tn_grouped(const AlmTnJob* jobs, int njobs, float* 
     hipStream_t st = (hipStream_t)stream;
     TnGroupTable tb;
     TnGroupPlan geo;
-    tn_group_geometry(jobs, njobs, S, &geo, &tb);
+    TnGroupPlacement pc;                                                    // (the plan's geometry again, this time with the placement: copied into the table)
+    tn_group_geometry(jobs, njobs, S, &geo, &pc);
+    for (int q = 0; q < pc.njobs; ++q) { tb.tiles[q] = pc.tiles[q]; tb.tiles_n[q] = pc.tiles_n[q]; tb.nunits[q] = pc.nunits[q]; tb.base[q] = pc.base[q]; }
+    tb.njobs = pc.njobs; tb.S = pc.S;
     TnReduceTable rt;
     rt.njobs = tb.njobs; rt.S = S; rt.first[0] = 0;
     long long wso = 0, rmax = 0;
@@ -2108,8 +1758,7 @@ extern "C" int alm_gemm_bf16_tn_grouped(const AlmTnJob* jobs, int njobs, float* 
         const long long gx = (rmax / 4 + 255) / 256;
         hipLaunchKernelGGL(tn_grouped_reduce_kernel, dim3((unsigned)(gx < 1 ? 1 : gx > 512 ? 512 : gx), rt.first[k]), dim3(256), 0, st, rt);
     }
-    ALM_LAUNCH_CHECK();
-    return 0;
+    return checked(0);
 }
 
 extern "C" int alm_transpose_bf16(const void* src, void* dst, int rows, int cols, long long ld_src, long long ld_dst, int rows_pad,
@@ -2150,8 +1799,7 @@ static int pack3_launch(const AlmPackJob* jobs, int njobs, hipStream_t st) {
 extern "C" int alm_pack_weights_multi(const AlmPackJob* jobs, int njobs, void* stream) {
     if (njobs <= 0) return 0;
     if (!jobs) return ALM_ERR_BAD_ARG;
-    static const int wide_on = [] { const char* e = getenv("ALM_PACK_WIDE"); return e ? atoi(e) : 1; }();     // A/B switch: 0 = the round-2 kernels
-    bool vec = true, wide = wide_on != 0;
+    bool vec = true, wide = gemm_env().pack_wide != 0;                      // (ALM_PACK_WIDE=0: the round-2 kernels)
     for (int j = 0; j < njobs; ++j) {
         const AlmPackJob& q = jobs[j];
         if (q.rows <= 0 || q.cols <= 0 || q.rows_pad < q.rows || q.cols_pad < q.cols) return ALM_ERR_BAD_ARG;

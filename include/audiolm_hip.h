@@ -69,7 +69,8 @@ int alm_gemm_splitk_slices(int M, int N, int K, int nb);
 int alm_gemm_splitk_ws_floats(int M, int N, int K, int nb);
 /* block tile of the split-K plan for this problem: 1 = 128 x 128 (4 waves), otherwise a 256 x 256 tile */
 int alm_gemm_splitk_tile(int M, int N, int K, int nb);
-/* host-side plan queries (no launch): the kernel a launch WILL take.
+/* host-side plan queries (no launch): the kernel a launch WILL take.  The launchers and these queries (alm_gemm_nt_plan and the split-K / grouped ones
+ * too) call ONE set of decision functions (csrc/gemm_plan.hpp, final_tile for the block tile), so a query cannot drift from the launch it describes.
  *   alm_gemm_nt_tile_choice: block tile of alm_gemm_bf16_nt(M, N) with nb = nb1 * nb2 problems: 1 = 128 x 128 (4 waves), 13 = 256 x 256 with staggered
  *     wave rows, 11 = 384 x 256 (the shipped choice; A/B environment hooks not applied)
  *   alm_gemm_tn_batched_plan: alm_gemm_bf16_tn_batched(M, N, K) over nb problems -> 0 = one full-K launch, 1 = uniform split-K (plan = {tile, slices, 0, 0}),

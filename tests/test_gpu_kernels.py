@@ -177,6 +177,28 @@ def test_gemm_nt_with_workspace_follows_its_plan(ops, M, N, K, nb):
     print(f'alm_gemm_nt_plan({M}, {N}, {K}, nb={nb}) -> tile {plan[0]}, {plan[1]} K slices, {plan[2]} workspace bytes, {plan[3]} workgroups')
 
 
+@pytest.mark.parametrize('M,N,K,tile,slices', [(5952, 2048, 128, 13, 1), (10304, 2048, 128, 11, 1), (16448, 1024, 128, 17, 1),
+                                               (2176, 2048, 128, 1, 1),      # 272 small tiles: one too many rounds for the ring form
+                                               (256, 256, 256, 16, 1), (256, 256, 3200, 13, 5)])
+def test_gemm_nt_automatic_route_is_the_tile_the_plan_names(ops, M, N, K, tile, slices):
+    """launch and plan query share one decision function (final_tile in csrc/gemm_plan.hpp): what ops.gemm_nt launches on its own is, bit for bit, the launch
+    of the tile alm_gemm_nt_plan names -- at the smallest M (steps of 64 rows) that reach tiles 13 / 11 / 17 at these N, a small-tile launch the ring form
+    must not take, one it must, and one tile the cost model cuts into 5 in-launch K slices"""
+    import ctypes
+    from audiolm_pytorch_amd import _lib
+    plan = (ctypes.c_int * 4)()
+    _lib.query('alm_gemm_nt_plan', M, N, K, 1, 1, ctypes.cast(plan, ctypes.c_void_p))
+    assert (plan[0], plan[1]) == (tile, slices), list(plan)
+    A, B = rnd(M, K, seed=61, dtype=BF16), rnd(N, K, seed=62, dtype=BF16)
+    C, C2 = torch.full((M, N), float('nan'), dtype=BF16, device=dev()), torch.full((M, N), float('nan'), dtype=BF16, device=dev())
+    ops.gemm_nt(A, B, C)
+    if plan[1] > 1:
+        ops.gemm_nt_inl(A, B, C2, plan[1])
+    else:
+        ops.gemm_nt_tile(A, B, C2, plan[0])
+    assert not bool(torch.isnan(C).any()) and torch.equal(C, C2)
+
+
 def test_gemm_nt_group2_small_tile_then_big_tile_in_one_process(ops):
     """round-5 advisor finding: the grouped launcher kept ONE dynamic-LDS attribute flag for its four kernels, so only the first variant launched in a process
     got hipFuncAttributeMaxDynamicSharedMemorySize.  A 128 x 128 pair (64 KB of LDS) followed by a staggered 256 x 256 pair (160 KB) in the same process, both
