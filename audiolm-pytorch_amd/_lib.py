@@ -167,6 +167,20 @@ SIGNATURES = {
     'alm_loss_ws_floats': [],
     'alm_loss_mean_fwd': [_P, _P, _P, _P, _L, _I, _P],
     'alm_loss_mean_bwd': [_P, _P, _P, _P, _P, _L, _I, _P],
+    'alm_stft_frames': [_I, _I, _I],
+    'alm_stft_fwd': [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    'alm_stft_bwd_ws_floats': [_I, _I, _I, _I],
+    'alm_stft_bwd': [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    'alm_cconv2d_out_hw': [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    'alm_cconv2d_fwd': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_cconv2d_dgrad': [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_cconv2d_wgrad_ws_floats': [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I],
+    'alm_cconv2d_wgrad': [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_modrelu_ws_floats': [],
+    'alm_modrelu_fwd': [_P, _P, _P, _L, _P],
+    'alm_modrelu_bwd': [_P, _P, _P, _P, _P, _P, _L, _P],
+    'alm_cabs_fwd': [_P, _P, _L, _P],
+    'alm_cabs_bwd': [_P, _P, _P, _L, _P],
     'alm_memset_zero': [_P, _L, _P],
     'alm_list_op_id': [ctypes.c_char_p],
     'alm_list_op_nargs': [_I],

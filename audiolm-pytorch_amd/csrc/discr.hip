@@ -14,7 +14,7 @@
 // The activation's derivative comes from the saved OUTPUT (y > 0 <=> pre-activation > 0), like the ELU path of codec_bwd.hip.
 //
 // AvgPool1d(2 f, stride f, padding f), count_include_pad: y[t] = sum_{i < 2f} x[t f - f + i] / (2 f); its adjoint gathers the <= 2 windows over u.
-// Loss reductions (hinge discriminator / hinge generator / L1 / squared error means): per-block partial sums over a contiguous span in a fixed lane
+// Loss reductions (hinge discriminator / hinge generator / L1 / squared error / complex L1 = mean modulus means): per-block partial sums over a contiguous span in a fixed lane
 // order, then one block adds the partials in index order; the backward is elementwise and takes the upstream gradient from device memory.
 #include "common.hpp"
 #include "../../include/audiolm_hip.h"
@@ -309,7 +309,11 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const float* __restri
                                                            long long span, int mode) {
     const long long lo = (long long)blockIdx.x * span, hi = min(n, lo + span);
     float s = 0.f;
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) s += loss_term(mode, a[i], b ? b[i] : 0.f);
+    if (mode == ALM_LOSS_L1_COMPLEX) {                              // n complex elements: the modulus of the difference of the (re, im) pairs
+        for (long long i = lo + threadIdx.x; i < hi; i += 256) s += hypotf(a[2 * i] - b[2 * i], a[2 * i + 1] - b[2 * i + 1]);
+    } else {
+        for (long long i = lo + threadIdx.x; i < hi; i += 256) s += loss_term(mode, a[i], b ? b[i] : 0.f);
+    }
     s = block_sum(s);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
@@ -326,6 +330,13 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float g = gout[0] * scale;
+    if (mode == ALM_LOSS_L1_COMPLEX) {                              // (a - b) / |a - b| g, 0 where a == b
+        const float dr = a[2 * i] - b[2 * i], di = a[2 * i + 1] - b[2 * i + 1], r = hypotf(dr, di);
+        const float gr = r > 0.f ? g * (dr / r) : 0.f, gi = r > 0.f ? g * (di / r) : 0.f;
+        if (da) da[2 * i] = gr, da[2 * i + 1] = gi;
+        if (db) db[2 * i] = -gr, db[2 * i + 1] = -gi;
+        return;
+    }
     float ga = 0.f, gb = 0.f;
     if (mode == ALM_LOSS_HINGE_DISCR) {
         ga = 1.f + a[i] > 0.f ? g : 0.f;
@@ -459,7 +470,7 @@ extern "C" int alm_avgpool1d_bwd(const float* g, float* dx, long long rows, int 
 extern "C" int alm_loss_ws_floats(void) { return RED_MAX_BLOCKS; }
 
 extern "C" int alm_loss_mean_fwd(const float* a, const float* b, float* out, float* ws, long long n, int mode, void* stream) {
-    if (n <= 0 || mode < ALM_LOSS_HINGE_DISCR || mode > ALM_LOSS_MSE || (mode != ALM_LOSS_HINGE_GEN && b == nullptr)) return ALM_ERR_BAD_ARG;
+    if (n <= 0 || mode < ALM_LOSS_HINGE_DISCR || mode > ALM_LOSS_L1_COMPLEX || (mode != ALM_LOSS_HINGE_GEN && b == nullptr)) return ALM_ERR_BAD_ARG;
     long long span = RED_SPAN;
     while ((n + span - 1) / span > RED_MAX_BLOCKS) span *= 2;
     const int nparts = (int)((n + span - 1) / span);
@@ -472,7 +483,7 @@ extern "C" int alm_loss_mean_fwd(const float* a, const float* b, float* out, flo
 }
 
 extern "C" int alm_loss_mean_bwd(const float* a, const float* b, const float* gout, float* da, float* db, long long n, int mode, void* stream) {
-    if (n <= 0 || mode < ALM_LOSS_HINGE_DISCR || mode > ALM_LOSS_MSE || (mode != ALM_LOSS_HINGE_GEN && b == nullptr)) return ALM_ERR_BAD_ARG;
+    if (n <= 0 || mode < ALM_LOSS_HINGE_DISCR || mode > ALM_LOSS_L1_COMPLEX || (mode != ALM_LOSS_HINGE_GEN && b == nullptr)) return ALM_ERR_BAD_ARG;
     if ((n + 255) / 256 >= 0x7fffffffLL) return ALM_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, gout, da, db, n,
                        (float)(1.0 / (double)n), mode);

@@ -6,6 +6,10 @@ reference training checkpoint load.  The kernels read a conv weight in nn.Conv1d
 an optimizer: every launch takes the parameter's current storage.  A graph is built only with grad mode on and an input or parameter that requires
 grad (train / eval mode makes no difference to these layers); otherwise a call issues the forward launches only.  Saved per conv: its input and, where
 LeakyReLU follows, its output (the activation's derivative is taken from the output's sign).  Gradients are bitwise reproducible (no atomics).
+
+`ComplexSTFTDiscriminator` (soundstream.py:173-310) follows the same rules on the kernels of csrc/stft_discr.hip: the STFT and every complex conv2d
+are implicit GEMMs on the exact-fp32 matrix core, the parameters keep the reference's names and real-view storage (`init_conv.*`,
+`layers.{i}.0.fn.{0,2}.*`, `layers.{i}.0.fn.1.b`, `layers.{i}.1.*`, `final_conv.*`), and `l1_loss` takes its complex64 intermediates.
 """
 from __future__ import annotations
 
@@ -121,6 +125,11 @@ def hinge_gen_loss(fake):                                        # soundstream.p
 
 
 def l1_loss(a, b):
+    """F.l1_loss; on a pair of complex64 tensors the mean modulus |a - b| over complex elements"""
+    if a.is_complex() or b.is_complex():
+        if a.dtype != torch.complex64 or b.dtype != torch.complex64:
+            raise TypeError(f'l1_loss: a complex pair must be complex64 on both sides; got {a.dtype} and {b.dtype}')
+        return _loss(ops.LOSS_L1_COMPLEX, torch.view_as_real(a), torch.view_as_real(b))
     return _loss(ops.LOSS_L1, a, b)
 
 
@@ -151,3 +160,192 @@ class MultiScaleDiscriminator(nn.Module):                        # soundstream.p
         if not return_intermediates:
             return out
         return out, intermediates
+
+
+# ---- ComplexSTFTDiscriminator (soundstream.py:173-310) on the kernels of csrc/stft_discr.hip.  Inside the module a complex activation travels as its
+# fp32 [..., 2] (re, im) view; the intermediates handed out are torch.complex64 views of the same storage (view_as_complex: no copy, no kernel).
+
+class _StftFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, basis, n_fft, hop):
+        ctx.cfg = (x.shape[1], n_fft, hop)
+        ctx.basis = basis
+        return ops.stft(x, basis, n_fft, hop)
+
+    @staticmethod
+    def backward(ctx, g):
+        n, n_fft, hop = ctx.cfg
+        return ops.stft_bwd(g.to(F32).contiguous(), ctx.basis, n, n_fft, hop), None, None, None
+
+
+class _CConv2dFn(torch.autograd.Function):
+    """conv2d of (re, im) pairs + bias (+ residual)"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, stride, padding):
+        ctx.cfg = (stride, padding)
+        ctx.save_for_backward(x, weight)
+        return ops.cconv2d(x, weight.detach(), bias.detach(), stride=stride, padding=padding, residual=residual)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        stride, padding = ctx.cfg
+        g = g.to(F32).contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.cconv2d_dgrad(g, weight.detach(), x.shape[2], x.shape[3], stride=stride, padding=padding)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = ops.cconv2d_wgrad(g, x, weight.shape[2:4], stride=stride, padding=padding)
+        return dx, dw, db, (g if ctx.needs_input_grad[3] else None), None, None
+
+
+class _ModReLUFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, b):
+        ctx.save_for_backward(z, b)
+        return ops.modrelu(z, b.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        z, b = ctx.saved_tensors
+        dz, db = ops.modrelu_bwd(g.to(F32).contiguous(), z, b.detach(), need_dz=ctx.needs_input_grad[0])
+        return dz, (db if ctx.needs_input_grad[1] else None)
+
+
+class _CAbsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z):
+        ctx.save_for_backward(z)
+        return ops.complex_abs(z)
+
+    @staticmethod
+    def backward(ctx, g):
+        z, = ctx.saved_tensors
+        return ops.complex_abs_bwd(g.to(F32).contiguous(), z)
+
+
+def _as_pairs(x):
+    """a complex64 tensor or its fp32 [..., 2] view -> the contiguous fp32 [..., 2] view"""
+    if x.is_complex():
+        if x.dtype != torch.complex64:
+            raise TypeError(f'the discriminator kernels are fp32 (complex64); got {x.dtype}')
+        x = torch.view_as_real(x)
+    return _f32c(x)
+
+
+class ModReLU(nn.Module):                                        # soundstream.py:173-183
+    def __init__(self):
+        super().__init__()
+        self.b = nn.Parameter(torch.tensor(0.))
+
+    def forward(self, z):
+        """z complex64 or fp32 [..., 2] -> fp32 [..., 2]; the scalar b is read on the device"""
+        z, b = _as_pairs(z), _f32c(self.b)
+        return _ModReLUFn.apply(z, b) if _needs_graph(z, self.b) else ops.modrelu(z.detach(), b.detach())
+
+
+class ComplexConv2d(nn.Module):                                  # soundstream.py:185-206
+    """weight [Cout, Cin, kh, kw, 2] and bias [Cout, 2] are view_as_real of a complex64 nn.Conv2d's parameters, initialised by that module on the CPU
+    like the reference does (the same torch.manual_seed gives the same values); the kernels read them as they are."""
+
+    def __init__(self, dim, dim_out, kernel_size, stride=1, padding=0):
+        super().__init__()
+        conv = nn.Conv2d(dim, dim_out, kernel_size, dtype=torch.complex64)
+        self.weight = nn.Parameter(torch.view_as_real(conv.weight))
+        self.bias = nn.Parameter(torch.view_as_real(conv.bias))
+        self.stride = stride
+        self.padding = padding
+
+    def forward(self, x, residual=None):
+        """x complex64 or fp32 [b, c, h, w, 2] -> fp32 [b, c', h', w', 2] (+ residual)"""
+        x, w, b = _as_pairs(x), _f32c(self.weight), _f32c(self.bias)
+        if _needs_graph(x, self.weight, self.bias, residual):
+            return _CConv2dFn.apply(x, w, b, residual, self.stride, self.padding)
+        return ops.cconv2d(x.detach(), w.detach(), b.detach(), stride=self.stride, padding=self.padding,
+                           residual=None if residual is None else residual.detach())
+
+
+class _ComplexResidual(nn.Module):                               # soundstream.py:314-320 around Sequential(conv, ModReLU, conv)
+    def __init__(self, fn):
+        super().__init__()
+        self.fn = fn
+
+    def forward(self, x):
+        x = _as_pairs(x)
+        return self.fn[2](self.fn[1](self.fn[0](x)), residual=x)     # the residual add is the second conv's epilogue
+
+
+def _complex_stft_residual_unit(chan_in, chan_out, strides):     # soundstream.py:208-219
+    kernel_sizes = tuple(s + 2 for s in strides)
+    paddings = tuple(k // 2 for k in kernel_sizes)
+    return nn.Sequential(
+        _ComplexResidual(nn.Sequential(ComplexConv2d(chan_in, chan_in, 3, padding=1), ModReLU(), ComplexConv2d(chan_in, chan_in, 3, padding=1))),
+        ComplexConv2d(chan_in, chan_out, kernel_sizes, stride=strides, padding=paddings))
+
+
+class ComplexSTFTDiscriminator(nn.Module):                       # soundstream.py:221-310
+    def __init__(self, *, channels=32, strides=((1, 2), (2, 2), (1, 2), (2, 2), (1, 2), (2, 2)), chan_mults=(1, 2, 4, 4, 8, 8), input_channels=1,
+                 n_fft=1024, hop_length=256, win_length=1024, stft_normalized=False, stft_window_fn=torch.hann_window, logits_abs=True):
+        super().__init__()
+        self.input_channels = input_channels
+        self.init_conv = ComplexConv2d(input_channels, channels, 7, padding=3)
+        layer_channels = (channels, *(m * channels for m in chan_mults))
+        self.layers = nn.ModuleList([_complex_stft_residual_unit(ci, co, tuple(s))
+                                     for s, (ci, co) in zip(strides, zip(layer_channels[:-1], layer_channels[1:]))])
+        self.final_conv = ComplexConv2d(layer_channels[-1], 1, (16, 1))
+        self.stft_normalized = stft_normalized
+        self.stft_window_fn = stft_window_fn
+        self.n_fft, self.hop_length, self.win_length = n_fft, hop_length, win_length
+        self.logits_abs = logits_abs
+
+    def _convs(self):
+        yield self.init_conv
+        for layer in self.layers:
+            yield from (layer[0].fn[0], layer[0].fn[2], layer[1])
+        yield self.final_conv
+
+    def check_geometry(self, n):
+        """the refusals that need no launch: the clip against the reflect padding, and every conv's input against its kernel (the frequency axis
+        against the final conv's 16 rows)"""
+        if self.input_channels != 1:
+            raise NotImplementedError("ComplexSTFTDiscriminator: input_channels != 1 (the reference's own rearrange 'b 1 n -> b n' does not admit it)")
+        T = ops.stft_frames(n, self.n_fft, self.hop_length)
+        if T < 1:
+            raise ValueError(f'ComplexSTFTDiscriminator: a clip of {n} samples is too short for the reflect padding of n_fft = {self.n_fft} '
+                             f'(needs more than {self.n_fft // 2})')
+        hw = (self.n_fft // 2 + 1, T)
+        for conv in self._convs():
+            out = ops.cconv2d_out_hw(*hw, tuple(conv.weight.shape[2:4]), conv.stride, conv.padding)
+            if out is None:
+                raise ValueError(f'ComplexSTFTDiscriminator: the frequency axis shrinks to {hw[0]} rows, fewer than the '
+                                 f'{conv.weight.shape[2]} rows of the final conv (n_fft = {self.n_fft} is too small for these strides)')
+            hw = out
+        return hw
+
+    def forward(self, x, return_intermediates=False):
+        """x fp32 (b, 1, n) -> logits: real (b, 1, f', t') with logits_abs, else the trailing-2 real view (b, 1, f', t', 2); with
+        return_intermediates also the complex64 outputs of init_conv and of every layer"""
+        self.check_geometry(x.shape[-1])
+        if x.ndim != 3 or x.shape[1] != 1:
+            raise ValueError(f'ComplexSTFTDiscriminator takes a wave of shape (b, 1, n); got {tuple(x.shape)}')
+        x = _f32c(x).reshape(x.shape[0], x.shape[-1])
+        window = self.stft_window_fn(self.win_length, device='cpu')
+        basis = ops.stft_basis(self.n_fft, window, self.stft_normalized, x.device)
+        if _needs_graph(x):                                          # the STFT has no parameters: its backward runs only for the wave
+            h = _StftFn.apply(x, basis, self.n_fft, self.hop_length)
+        else:
+            h = ops.stft(x.detach(), basis, self.n_fft, self.hop_length)
+        h = self.init_conv(h.unsqueeze(1))
+        intermediates = [h]
+        for layer in self.layers:
+            h = layer[1](layer[0](h))
+            intermediates.append(h)
+        z = self.final_conv(h)
+        if self.logits_abs:
+            logits = _CAbsFn.apply(z) if _needs_graph(z) else ops.complex_abs(z)
+        else:
+            logits = z
+        if not return_intermediates:
+            return logits
+        return logits, [torch.view_as_complex(t) for t in intermediates]

@@ -4,6 +4,7 @@ memory and the stream; all arithmetic happens in libaudiolm_hip.so.  No CPU / ea
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import torch
@@ -1639,13 +1640,14 @@ def avgpool1d_bwd(g, T, f):
 
 def loss_mean(mode, a, b=None):
     """0-dim fp32 mean over all elements, summed in a fixed order: LOSS_HINGE_DISCR relu(1 + a) + relu(1 - b) (a fake, b real logits),
-    LOSS_HINGE_GEN -a, LOSS_L1 |a - b|, LOSS_MSE (a - b)^2"""
+    LOSS_HINGE_GEN -a, LOSS_L1 |a - b|, LOSS_MSE (a - b)^2, LOSS_L1_COMPLEX the modulus |a - b| of [..., 2] (re, im) pairs, the mean over complex elements"""
     assert _chk(a, F32).is_contiguous() and (b is None) == (mode == LOSS_HINGE_GEN)
+    assert mode != LOSS_L1_COMPLEX or a.shape[-1] == 2
     if b is not None:
         assert _chk(b, F32).is_contiguous() and b.shape == a.shape
     out = _new((), dtype=F32, device=a.device)
     ws = _new((_lib.query('alm_loss_ws_floats'),), dtype=F32, device=a.device)
-    _lib.call('alm_loss_mean_fwd', a.data_ptr(), _p(b), out.data_ptr(), ws.data_ptr(), a.numel(), mode, _st())
+    _lib.call('alm_loss_mean_fwd', a.data_ptr(), _p(b), out.data_ptr(), ws.data_ptr(), a.numel() // (2 if mode == LOSS_L1_COMPLEX else 1), mode, _st())
     return out
 
 
@@ -1654,5 +1656,164 @@ def loss_mean_bwd(mode, a, b, gout, need_a=True, need_b=True):
     assert _chk(gout, F32).numel() == 1
     da = _new_like(a) if need_a else None
     db = _new_like(b) if need_b and b is not None else None
-    _lib.call('alm_loss_mean_bwd', a.data_ptr(), _p(b), gout.data_ptr(), _p(da), _p(db), a.numel(), mode, _st())
+    _lib.call('alm_loss_mean_bwd', a.data_ptr(), _p(b), gout.data_ptr(), _p(da), _p(db), a.numel() // (2 if mode == LOSS_L1_COMPLEX else 1), mode, _st())
     return da, db
+
+
+# ---- ComplexSTFTDiscriminator of SoundStream training (csrc/stft_discr.hip), fp32, no atomics.  Complex tensors travel as fp32 [..., 2] (re, im) pairs.
+
+LOSS_L1_COMPLEX = 4
+_STFT_BASIS = {}
+
+
+def stft_frames(n, n_fft, hop_length):
+    """frames of torch.stft(center=True) on a clip of n samples; -1 unless n > n_fft / 2 (reflect padding needs it)"""
+    return _lib.query('alm_stft_frames', n, n_fft, hop_length)
+
+
+def stft_basis(n_fft, window, normalized, device, onesided=True):
+    """windowed DFT basis fp32 [n_fft, 2 F] on `device`: column 2 f = w[k] cos(2 pi f k / n_fft), 2 f + 1 = -w[k] sin(.); `window` is a CPU tensor of
+    win_length <= n_fft values, zero-padded and centred.  Built in float64, rounded once, cached per (n_fft, window values, normalized, device)."""
+    w = window.detach().to('cpu', torch.float64).reshape(-1)
+    assert 0 < w.numel() <= n_fft, (w.numel(), n_fft)
+    key = (n_fft, w.numel(), w.numpy().tobytes(), bool(normalized), bool(onesided), str(device))
+    hit = _STFT_BASIS.get(key)
+    if hit is None:
+        F = n_fft // 2 + 1 if onesided else n_fft
+        left = (n_fft - w.numel()) // 2
+        wp = torch.zeros(n_fft, dtype=torch.float64)
+        wp[left:left + w.numel()] = w
+        if normalized:
+            wp = wp * float(n_fft) ** -0.5
+        k = torch.arange(n_fft, dtype=torch.int64)
+        ang = ((k[:, None] * torch.arange(F, dtype=torch.int64)[None, :]) % n_fft).to(torch.float64) * (2. * math.pi / n_fft)
+        basis = torch.stack((wp[:, None] * torch.cos(ang), -wp[:, None] * torch.sin(ang)), dim=-1).reshape(n_fft, 2 * F)
+        if len(_STFT_BASIS) >= 16:
+            _STFT_BASIS.clear()
+        hit = _STFT_BASIS[key] = basis.to(F32).to(device)
+    return hit
+
+
+def stft(x, basis, n_fft, hop_length):
+    """x fp32 [B, n] -> X fp32 [B, F, T, 2] = view_as_real(torch.stft(x, n_fft, hop_length, window=..., center=True, pad_mode='reflect',
+    return_complex=True)), the window (and `normalized`) inside `basis` (stft_basis)"""
+    assert _chk(x, F32).is_contiguous() and x.ndim == 2 and _chk(basis, F32).is_contiguous() and basis.shape[0] == n_fft and basis.shape[1] % 2 == 0
+    B, n = x.shape
+    T, F = stft_frames(n, n_fft, hop_length), basis.shape[1] // 2
+    if T < 1:
+        raise _lib.AlmError(f'stft: a clip of {n} samples is too short for the reflect padding of n_fft = {n_fft} (needs more than n_fft / 2)')
+    X = _new((B, F, T, 2), dtype=F32, device=x.device)
+    _lib.call('alm_stft_fwd', x.data_ptr(), basis.data_ptr(), X.data_ptr(), B, n, n_fft, hop_length, F, _st())
+    return X
+
+
+def stft_bwd(dX, basis, n, n_fft, hop_length):
+    """dX fp32 [B, F, T, 2] -> dx fp32 [B, n]: the adjoint of stft (transposed product, overlap-add, fold of the reflect padding)"""
+    assert _chk(dX, F32).is_contiguous() and dX.ndim == 4 and _chk(basis, F32).is_contiguous()
+    B, F, T, _ = dX.shape
+    assert basis.shape == (n_fft, 2 * F) and T == stft_frames(n, n_fft, hop_length)
+    nws = _lib.query('alm_stft_bwd_ws_floats', B, n, n_fft, hop_length)
+    if nws < 0:
+        raise _lib.AlmError('stft_bwd: shape outside the kernel envelope')
+    ws = _new((nws,), dtype=F32, device=dX.device)
+    dx = _new((B, n), dtype=F32, device=dX.device)
+    _lib.call('alm_stft_bwd', dX.data_ptr(), basis.data_ptr(), dx.data_ptr(), ws.data_ptr(), nws, B, n, n_fft, hop_length, F, _st())
+    return dx
+
+
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def cconv2d_out_hw(H, W, kernel_size, stride=1, padding=0):
+    """(Ho, Wo) of a zero-padded undilated conv2d, or None when the padded input is smaller than the kernel"""
+    (kh, kw), (sh, sw), (ph, pw) = _pair(kernel_size), _pair(stride), _pair(padding)
+    ho, wo = ctypes.c_int(0), ctypes.c_int(0)
+    if _lib.query('alm_cconv2d_out_hw', H, W, kh, kw, sh, sw, ph, pw, ctypes.byref(ho), ctypes.byref(wo)) != 0:
+        return None
+    return ho.value, wo.value
+
+
+def _cconv_dims(xshape, wshape, stride, padding):
+    B, Cin, H, W, two = xshape
+    Cout, Cin_w, kh, kw, two_w = wshape
+    assert two == 2 and two_w == 2 and Cin_w == Cin, (tuple(xshape), tuple(wshape))
+    (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
+    out = cconv2d_out_hw(H, W, (kh, kw), (sh, sw), (ph, pw))
+    if out is None:
+        raise _lib.AlmError(f'cconv2d: the padded input ({H} + 2 * {ph}, {W} + 2 * {pw}) is smaller than the kernel ({kh}, {kw})')
+    return (B, Cin, Cout, H, W, kh, kw, sh, sw, ph, pw), out
+
+
+def cconv2d(x, w, bias, *, stride=1, padding=0, residual=None):
+    """x fp32 [B, Cin, H, W, 2], w fp32 [Cout, Cin, kh, kw, 2], bias fp32 [Cout, 2] (view_as_real of a complex nn.Conv2d's parameters)
+    -> view_as_real(F.conv2d(x, w, bias, stride, padding)) fp32 [B, Cout, Ho, Wo, 2] (+ residual of that shape)"""
+    assert all(_chk(t, F32).is_contiguous() for t in (x, w, bias))
+    dims, (Ho, Wo) = _cconv_dims(x.shape, w.shape, stride, padding)
+    assert bias.shape == (dims[2], 2)
+    y = _new((dims[0], dims[2], Ho, Wo, 2), dtype=F32, device=x.device)
+    if residual is not None:
+        assert _chk(residual, F32).is_contiguous() and residual.shape == y.shape
+    _lib.call('alm_cconv2d_fwd', x.data_ptr(), w.data_ptr(), bias.data_ptr(), _p(residual), y.data_ptr(), *dims, _st())
+    return y
+
+
+def cconv2d_dgrad(g, w, H, W, *, stride=1, padding=0):
+    """g fp32 [B, Cout, Ho, Wo, 2] = dL/dy -> dL/dx fp32 [B, Cin, H, W, 2] of cconv2d"""
+    assert all(_chk(t, F32).is_contiguous() for t in (g, w))
+    dims, (Ho, Wo) = _cconv_dims((g.shape[0], w.shape[1], H, W, 2), w.shape, stride, padding)
+    assert g.shape == (dims[0], dims[2], Ho, Wo, 2), (tuple(g.shape), dims, Ho, Wo)
+    dx = _new((dims[0], dims[1], H, W, 2), dtype=F32, device=g.device)
+    _lib.call('alm_cconv2d_dgrad', g.data_ptr(), w.data_ptr(), dx.data_ptr(), *dims, _st())
+    return dx
+
+
+def cconv2d_wgrad(g, x, kernel_size, *, stride=1, padding=0):
+    """g fp32 [B, Cout, Ho, Wo, 2], x fp32 [B, Cin, H, W, 2] -> (dW fp32 [Cout, Cin, kh, kw, 2], db fp32 [Cout, 2]); per-split partial sums in a
+    workspace of alm_cconv2d_wgrad_ws_floats floats, added in split order."""
+    assert all(_chk(t, F32).is_contiguous() for t in (g, x))
+    kh, kw = _pair(kernel_size)
+    dims, (Ho, Wo) = _cconv_dims(x.shape, (g.shape[1], x.shape[1], kh, kw, 2), stride, padding)
+    assert g.shape == (dims[0], dims[2], Ho, Wo, 2), (tuple(g.shape), dims, Ho, Wo)
+    n = _lib.query('alm_cconv2d_wgrad_ws_floats', *dims)
+    if n < 0:
+        raise _lib.AlmError('cconv2d_wgrad: shape outside the kernel envelope (index / workspace limits)')
+    ws = _new((n,), dtype=F32, device=g.device)
+    dw = _new((dims[2], dims[1], kh, kw, 2), dtype=F32, device=g.device)
+    db = _new((dims[2], 2), dtype=F32, device=g.device)
+    _lib.call('alm_cconv2d_wgrad', g.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), n, *dims, _st())
+    return dw, db
+
+
+def modrelu(z, b):
+    """z fp32 [..., 2], b fp32 scalar ON THE DEVICE (never read by the host) -> relu(|z| + b) z / |z| (relu(b) + 0i at z = 0)"""
+    assert _chk(z, F32).is_contiguous() and z.shape[-1] == 2 and _chk(b, F32).numel() == 1
+    y = _new_like(z)
+    _lib.call('alm_modrelu_fwd', z.data_ptr(), b.data_ptr(), y.data_ptr(), z.numel() // 2, _st())
+    return y
+
+
+def modrelu_bwd(g, z, b, need_dz=True):
+    """(dz | None, db 0-dim) of modrelu; db is summed in two fixed-order stages"""
+    assert all(_chk(t, F32).is_contiguous() for t in (g, z)) and g.shape == z.shape and _chk(b, F32).numel() == 1
+    dz = _new_like(z) if need_dz else None
+    db = _new((), dtype=F32, device=z.device)
+    ws = _new((_lib.query('alm_modrelu_ws_floats'),), dtype=F32, device=z.device)
+    _lib.call('alm_modrelu_bwd', g.data_ptr(), z.data_ptr(), b.data_ptr(), _p(dz), db.data_ptr(), ws.data_ptr(), z.numel() // 2, _st())
+    return dz, db
+
+
+def complex_abs(z):
+    """z fp32 [..., 2] -> |z| fp32 [...]"""
+    assert _chk(z, F32).is_contiguous() and z.shape[-1] == 2
+    y = _new(tuple(z.shape[:-1]), dtype=F32, device=z.device)
+    _lib.call('alm_cabs_fwd', z.data_ptr(), y.data_ptr(), y.numel(), _st())
+    return y
+
+
+def complex_abs_bwd(g, z):
+    """g fp32 [...], z fp32 [..., 2] -> g z / |z| (0 at z = 0)"""
+    assert all(_chk(t, F32).is_contiguous() for t in (g, z)) and tuple(z.shape) == (*g.shape, 2)
+    dz = _new_like(z)
+    _lib.call('alm_cabs_bwd', g.data_ptr(), z.data_ptr(), dz.data_ptr(), g.numel(), _st())
+    return dz

@@ -4,8 +4,8 @@ return_codes_only=True)` -- the causal-conv encoder (soundstream.py:332-380, 519
 (soundstream.py:592-607, :840) -- and `decode_from_codebook_indices` / `decode` (soundstream.py:691-709: code lookup, transposed-conv
 decoder :347-360, 382-395, 615-627) run on the MI355X kernels of csrc/codec.hip (exact-fp32 MFMA).  The training losses (soundstream.py:868-995:
 three wave MultiScaleDiscriminators, hinge / feature / reconstruction terms) are opt-in, `with_discriminators=True` (discriminators.py,
-csrc/discr.hip); the default ComplexSTFTDiscriminator, the mel-spectrogram loss, the gradient penalty and the LFQ / FSQ quantizers are out of scope
-and raise.  In training mode the quantizer takes one
+csrc/discr.hip), and so is the ComplexSTFTDiscriminator, `stft_discriminator=True` (csrc/stft_discr.hip); the mel-spectrogram loss, the gradient
+penalty and the LFQ / FSQ quantizers are out of scope and raise.  In training mode the quantizer takes one
 training step per call (csrc/rvq_train.hip: quantize dropout, commitment loss, rotation trick, EMA codebooks with dead-code expiry, k-means
 initialisation; single process only), so `forward(x, return_recons_only=True | return_encoded=True)` is differentiable end to end.  The conv encoder / decoder are
 differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
@@ -546,7 +546,8 @@ class SoundStream(nn.Module):
                  enc_cycle_dilations=(1, 3, 9), recon_loss_weight=1., multi_spectral_recon_loss_weight=1e-5, adversarial_loss_weight=1.,
                  feature_loss_weight=100, target_sample_hz=16000, use_local_attn=True, attn_window_size=128, attn_dim_head=64, attn_heads=8, attn_depth=1,
                  attn_xpos_scale_base=None, attn_dynamic_pos_bias=False, use_gate_loop_layers=False, squeeze_excite=False, pad_mode='reflect',
-                 stft_discriminator=None, with_discriminators=False, **kwargs):
+                 stft_discriminator=None, with_discriminators=False, stft_normalized=False, complex_stft_discr_logits_abs=True,
+                 complex_stft_discr_kwargs: dict = {}, **kwargs):
         super().__init__()
         if use_lookup_free_quantizer or use_finite_scalar_quantizer or finite_scalar_quantizer_levels is not None:
             raise NotImplementedError('LFQ / FSQ quantizers are out of scope (SURVEY.md §2)')
@@ -591,9 +592,13 @@ class SoundStream(nn.Module):
             factors = [int(s1 / s2) for s1, s2 in zip(discr_multi_scales[:-1], discr_multi_scales[1:])]
             self.downsamples = nn.ModuleList([nn.Identity()] + [D.AvgPoolDownsample(f) for f in factors])
             if isinstance(stft_discriminator, nn.Module):
-                self.stft_discriminator = stft_discriminator     # the caller's module, run by PyTorch as it is
+                self.stft_discriminator = stft_discriminator     # the caller's module, run as it is (a D.ComplexSTFTDiscriminator: on the HIP kernels)
+            elif stft_discriminator is True:                     # the reference's default module (soundstream.py:638-643), native
+                self.stft_discriminator = D.ComplexSTFTDiscriminator(stft_normalized=stft_normalized, logits_abs=complex_stft_discr_logits_abs,
+                                                                     **complex_stft_discr_kwargs)
             elif stft_discriminator not in (None, False):
-                raise TypeError('stft_discriminator: an nn.Module with forward(x, return_intermediates=False), False (train without one) or None')
+                raise TypeError('stft_discriminator: True (the native ComplexSTFTDiscriminator), an nn.Module with '
+                                'forward(x, return_intermediates=False), False (train without one) or None')
         self.eval()
 
     @property
@@ -690,8 +695,9 @@ class SoundStream(nn.Module):
             raise NotImplementedError('apply_grad_penalty=True (gradient penalty) needs a double backward through the discriminator kernels, which is '
                                       'not implemented')
         if getattr(self, 'stft_discriminator', None) is None and not self._stft_discriminator_off:
-            raise NotImplementedError('the default ComplexSTFTDiscriminator is not implemented: pass stft_discriminator=<an nn.Module with '
-                                      'forward(x, return_intermediates=False)>, or stft_discriminator=False to train without one')
+            raise NotImplementedError('the ComplexSTFTDiscriminator is not constructed by default: pass stft_discriminator=True for the native one, '
+                                      'stft_discriminator=<an nn.Module with forward(x, return_intermediates=False)>, or stft_discriminator=False '
+                                      'to train without one')
 
     def _scales(self, real, fake):
         """per wave discriminator (logits, intermediates) of real and fake run as ONE batch [real | fake] through the chain of downsamples"""
@@ -702,10 +708,25 @@ class SoundStream(nn.Module):
             logits, inter = discr(scaled, return_intermediates=True)
             yield (logits[:b], logits[b:]), [(t[:b], t[b:]) for t in inter]
 
+    def _stft(self, real, fake, return_intermediates):
+        """(real, fake) outputs of the STFT discriminator: the native module takes ONE batch [real | fake] like `_scales` (every op is
+        batch-independent); a caller's own module gets its two separate calls"""
+        discr = self.stft_discriminator
+        if not isinstance(discr, D.ComplexSTFTDiscriminator):
+            if return_intermediates:
+                return discr(real, return_intermediates=True), discr(fake, return_intermediates=True)
+            return discr(real), discr(fake)
+        b = real.shape[0]
+        out = discr(torch.cat((real, fake), dim=0), return_intermediates=return_intermediates)
+        if not return_intermediates:
+            return out[:b], out[b:]
+        logits, inter = out
+        return (logits[:b], [t[:b] for t in inter]), (logits[b:], [t[b:] for t in inter])
+
     def _discr_loss(self, real, fake, separately):               # soundstream.py:870-925 (without the gradient penalties)
         stft_loss = None
         if not self._stft_discriminator_off and self.single_channel:
-            stft_real_logits, stft_fake_logits = self.stft_discriminator(real), self.stft_discriminator(fake)
+            stft_real_logits, stft_fake_logits = self._stft(real, fake, False)
             stft_loss = D.hinge_discr_loss(stft_fake_logits, stft_real_logits)
         losses = [D.hinge_discr_loss(fake_logits, real_logits) for (real_logits, fake_logits), _ in self._scales(real, fake)]
         if not separately:
@@ -722,8 +743,7 @@ class SoundStream(nn.Module):
         adversarial, pairs = [], []
         stft_fake_logits = None
         if not self._stft_discriminator_off:
-            _, stft_real_inter = self.stft_discriminator(real, return_intermediates=True)
-            stft_fake_logits, stft_fake_inter = self.stft_discriminator(fake, return_intermediates=True)
+            (_, stft_real_inter), (stft_fake_logits, stft_fake_inter) = self._stft(real, fake, True)
             pairs.extend(zip(stft_real_inter, stft_fake_inter))
         for (_, fake_logits), inter in self._scales(real, fake):
             adversarial.append(D.hinge_gen_loss(fake_logits))

@@ -579,12 +579,14 @@ int alm_lstm_seq(const float* xproj, const float* w_ih, const float* w_hh, const
  *                       (alm_gconv1d_wgrad_ws_floats floats, caller-owned; -1: outside the kernel's envelope), then added in split order.
  * alm_avgpool1d_* : AvgPool1d(2 f, stride f, padding f), count_include_pad; x [rows][T] -> y [rows][T / f + 1] (alm_avgpool1d_out_len) and its adjoint.
  * alm_loss_mean_fwd : out[0] = mean of the mode's term over n elements, summed in a fixed order (ws: alm_loss_ws_floats floats):
- *     ALM_LOSS_HINGE_DISCR relu(1 + a) + relu(1 - b) (a = fake, b = real logits), ALM_LOSS_HINGE_GEN -a (b unused), ALM_LOSS_L1 |a - b|, ALM_LOSS_MSE (a - b)^2.
+ *     ALM_LOSS_HINGE_DISCR relu(1 + a) + relu(1 - b) (a = fake, b = real logits), ALM_LOSS_HINGE_GEN -a (b unused), ALM_LOSS_L1 |a - b|, ALM_LOSS_MSE (a - b)^2,
+ *     ALM_LOSS_L1_COMPLEX the modulus |a - b| of interleaved (re, im) pairs with n counted in complex elements (F.l1_loss on complex tensors).
  * alm_loss_mean_bwd : da, db (either may be null) = gout[0] / n * d term / d a, d b; gout is read from device memory. */
 #define ALM_LOSS_HINGE_DISCR 0
 #define ALM_LOSS_HINGE_GEN 1
 #define ALM_LOSS_L1 2
 #define ALM_LOSS_MSE 3
+#define ALM_LOSS_L1_COMPLEX 4
 int alm_gconv1d_out_len(int Tin, int ksize, int stride, int padding);
 int alm_gconv1d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int Tin, int ksize, int stride, int padding,
                     int groups, int act, void* stream);
@@ -599,6 +601,43 @@ int alm_avgpool1d_bwd(const float* g, float* dx, long long rows, int T, int f, v
 int alm_loss_ws_floats(void);
 int alm_loss_mean_fwd(const float* a, const float* b, float* out, float* ws, long long n, int mode, void* stream);
 int alm_loss_mean_bwd(const float* a, const float* b, const float* gout, float* da, float* db, long long n, int mode, void* stream);
+
+/* ---- ComplexSTFTDiscriminator of SoundStream training (csrc/stft_discr.hip), fp32, no atomics -------------------------------------------------------
+ * Complex tensors are interleaved (re, im) pairs (torch.complex64's storage); a gradient is the pair (dL/dre, dL/dim) (reference soundstream.py:173-310).
+ * Every matrix product is an implicit GEMM on the exact-fp32 matrix core.
+ * alm_stft_fwd : x [B][n] -> X [B][F][T][2], torch.stft(center=True, pad_mode='reflect') with T = alm_stft_frames = (n + 2 (n_fft / 2) - n_fft) / hop + 1
+ *     (-1 unless n > n_fft / 2: one reflection must land inside the clip; the launchers then return ALM_ERR_UNSUPPORTED).  basis [n_fft][2 F]: column
+ *     2 f = w[k] cos(2 pi f k / n_fft), 2 f + 1 = -w[k] sin(.), the window zero-padded and centred to n_fft, times n_fft^-0.5 when normalized; F <= n_fft.
+ *     The reflect padding is index mirroring inside the operand load.
+ * alm_stft_bwd : dx [B][n] from dX: the frames' gradient [n_fft][B T] into ws (alm_stft_bwd_ws_floats floats; -1: outside the envelope), then every
+ *     sample gathers its own sum over its padded positions (itself, its mirrors) and the frames covering each, in a fixed order.
+ * alm_cconv2d_* : zero-padded complex conv2d, dilation 1.  x [B][Cin][H][W][2], w [Cout][Cin][kh][kw][2] and bias [Cout][2] (view_as_real of a complex
+ *     nn.Conv2d's parameters, read as they are), y [B][Cout][Ho][Wo][2] = conv + bias (+ residual [B][Cout][Ho][Wo][2] when not null).
+ *     alm_cconv2d_out_hw writes Ho = (H + 2 ph - kh) / sh + 1 and Wo and returns 0, or -1 when the padded input is smaller than the kernel.
+ *   alm_cconv2d_dgrad : dx [B][Cin][H][W][2] from g = dL/dy.
+ *   alm_cconv2d_wgrad : dw in the parameter's layout, db [Cout][2]; partial sums per split of the (b, ho, wo) list into ws
+ *                       (alm_cconv2d_wgrad_ws_floats floats, caller-owned; -1: outside the kernel's envelope), then added in split order.
+ * alm_modrelu_fwd : y = relu(|z| + b) z / |z| over n complex elements, b a scalar in device memory; z = 0 gives relu(b) + 0i.
+ * alm_modrelu_bwd : where |z| + b > 0, with u = z / |z|: dz = g + b (g - u (u . g)) / |z| and db += u . g (at z = 0: dz = 0, db += g_re); else 0.
+ *     dz may be null; db[0] is summed in two fixed-order stages through ws (alm_modrelu_ws_floats floats).
+ * alm_cabs_fwd / _bwd : y = |z| [n] and dz = g z / |z| (0 at z = 0). */
+int alm_stft_frames(int n, int n_fft, int hop);
+int alm_stft_fwd(const float* x, const float* basis, float* X, int B, int n, int n_fft, int hop, int F, void* stream);
+int alm_stft_bwd_ws_floats(int B, int n, int n_fft, int hop);
+int alm_stft_bwd(const float* dX, const float* basis, float* dx, float* ws, long long ws_floats, int B, int n, int n_fft, int hop, int F, void* stream);
+int alm_cconv2d_out_hw(int H, int W, int kh, int kw, int sh, int sw, int ph, int pw, int* Ho, int* Wo);
+int alm_cconv2d_fwd(const float* x, const float* w, const float* bias, const float* residual, float* y, int B, int Cin, int Cout, int H, int W, int kh,
+                    int kw, int sh, int sw, int ph, int pw, void* stream);
+int alm_cconv2d_dgrad(const float* g, const float* w, float* dx, int B, int Cin, int Cout, int H, int W, int kh, int kw, int sh, int sw, int ph, int pw,
+                      void* stream);
+int alm_cconv2d_wgrad_ws_floats(int B, int Cin, int Cout, int H, int W, int kh, int kw, int sh, int sw, int ph, int pw);
+int alm_cconv2d_wgrad(const float* g, const float* x, float* dw, float* db, float* ws, long long ws_floats, int B, int Cin, int Cout, int H, int W, int kh,
+                      int kw, int sh, int sw, int ph, int pw, void* stream);
+int alm_modrelu_ws_floats(void);
+int alm_modrelu_fwd(const float* z, const float* b, float* y, long long n, void* stream);
+int alm_modrelu_bwd(const float* g, const float* z, const float* b, float* dz, float* db, float* ws, long long n, void* stream);
+int alm_cabs_fwd(const float* z, float* y, long long n, void* stream);
+int alm_cabs_bwd(const float* g, const float* z, float* dz, long long n, void* stream);
 
 /* ---- launch lists (round 6): a recorded sequence of the launches above re-issued by ONE host call ---------------------------------------------
  * The depth loop of audiolm_pytorch.py:528-547 (Transformer.forward) and its backward are ~190 launches per training step whose ORDER and scalar arguments

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr]"""
 import os
 import sys
 import time
@@ -764,6 +764,94 @@ def bench_discr():
             torch.autograd.grad(torch.stack(losses).mean(), params)
         t_o, t_a = pair(ours_step, aten_step)
         print(f'discr 8 x {secs} s: discriminator-loss step (3 scales, fwd + bwd): hand {t_o:.2f} ms   ATen {t_a:.2f} ms   hand / ATen {t_o / t_a:.2f}', flush=True)
+
+
+def bench_stft_discr():
+    """ComplexSTFTDiscriminator of SoundStream training at 8 x 1 s and 8 x 10 s of 16 kHz audio (real and fake as one batch of 16): forward + backward
+    of the native module at its defaults (input and parameter gradients) and each of its conv forms alone (forward + dgrad + wgrad) on the kernels of
+    csrc/stft_discr.hip, against the SAME computation issued through PyTorch-ROCm (tests/stft_discr_restated.py moved to the GPU: torch.stft + complex
+    F.conv2d, fp32) on the same box.  The conv launches' achieved FLOP/s (8 real FLOP per complex multiply-accumulate) is printed as a fraction of
+    the 155 TFLOP/s exact-fp32 matrix peak.  Interleaved rounds, medians, one event pair per call."""
+    import torch.nn.functional as F
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    from stft_discr_restated import ComplexSTFTDiscriminatorRestated
+    from audiolm_pytorch_amd import ops
+    PEAK = 155e12
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def median(fns, rounds, warm):
+        for _ in range(warm):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(rounds):
+            for t, fn in zip(ts, fns):
+                t.append(once(fn))
+        return [sorted(t)[len(t) // 2] for t in ts]
+
+    torch.manual_seed(0)
+    m = A.ComplexSTFTDiscriminator().to(dev)
+    ref = ComplexSTFTDiscriminatorRestated()
+    ref.load_state_dict(m.state_dict())
+    ref.to(dev)
+    aten_ok = True
+    try:
+        ref(torch.randn(1, 1, 4096, device=dev))[0].sum().backward()
+        torch.cuda.synchronize()
+    except Exception as e:                                       # no complex conv on this build: say so and time ours alone
+        aten_ok = False
+        print(f'stft_discr: ATen cannot run the complex conv on this build ({type(e).__name__}: {str(e)[:120]}); timing the native path alone', flush=True)
+
+    def fwd_bwd(mod, x):
+        logits, inter = mod(x, return_intermediates=True)
+        loss = logits.mean() + sum(torch.view_as_real(t).mean() for t in inter)
+        torch.autograd.grad(loss, [x, *mod.parameters()])
+
+    for secs in (1, 10):
+        n = 16000 * secs
+        x = (torch.randn(16, 1, n, device=dev) * 0.3).requires_grad_()
+        rounds, warm = (8, 2) if secs == 1 else (3, 1)
+        fns = [lambda: fwd_bwd(m, x)] + ([lambda: fwd_bwd(ref, x)] if aten_ok else [])
+        ts = median(fns, rounds, warm)
+        tail = f'   ATen {ts[1]:.2f} ms   hand / ATen {ts[0] / ts[1]:.2f}' if aten_ok else ''
+        print(f'stft_discr 8 x {secs} s: ComplexSTFTDiscriminator fwd + bwd (batch 16 x {n}): hand {ts[0]:.2f} ms{tail}', flush=True)
+        basis = ops.stft_basis(m.n_fft, torch.hann_window(m.win_length), False, dev)
+        with torch.no_grad():
+            h = ops.stft(x.detach().reshape(16, n), basis, m.n_fft, m.hop_length).unsqueeze(1)
+        for name, conv in [('init_conv', m.init_conv), *((f'layers.{i}.{j}', c) for i, l in enumerate(m.layers)
+                                                         for j, c in (('0.fn.0', l[0].fn[0]), ('1', l[1]))), ('final_conv', m.final_conv)]:
+            hin = h.clone().requires_grad_()
+            wc, bc = torch.view_as_complex(conv.weight.detach()).requires_grad_(), torch.view_as_complex(conv.bias.detach()).requires_grad_()
+            hc = torch.view_as_complex(hin.detach()).requires_grad_()
+
+            def ours_layer():
+                y = conv(hin)
+                torch.autograd.grad(y.mean(), [hin, conv.weight, conv.bias])
+
+            def aten_layer():
+                y = F.conv2d(hc, wc, bc, stride=conv.stride, padding=conv.padding)
+                torch.autograd.grad(torch.view_as_real(y).mean(), [hc, wc, bc])
+            ts = median([ours_layer] + ([aten_layer] if aten_ok else []), rounds, warm)
+            with torch.no_grad():
+                y = conv(hin.detach())
+            Cout, Cin, kh, kw, _ = conv.weight.shape
+            flop = 3 * 8. * Cout * Cin * kh * kw * y.shape[0] * y.shape[2] * y.shape[3]            # forward + dgrad + wgrad
+            rate = flop / (ts[0] * 1e-3)
+            tail = f'   ATen {ts[1]:.3f} ms   hand / ATen {ts[0] / ts[1]:.2f}' if aten_ok else ''
+            print(f'    {name:16s} {Cin:4d} -> {Cout:4d} k{kh}x{kw} s{conv.stride} in {tuple(hin.shape[2:4])}: hand {ts[0]:.3f} ms '
+                  f'({rate / 1e12:.2f} TFLOP/s, {100 * rate / PEAK:.1f} % of the fp32 matrix peak){tail}', flush=True)
+            h = y
+            if name.endswith('0.fn.0'):                          # the unit's second 3 x 3 conv has the first one's form: step over it
+                with torch.no_grad():
+                    h = hin.detach()
 
 
 if __name__ == '__main__':
