@@ -20,6 +20,7 @@ from .audiolm_pytorch import (AudioLM, CoarseTransformer, CoarseTransformerWrapp
 from .discriminators import ComplexSTFTDiscriminator, MultiScaleDiscriminator
 from .encodec import EncodecWrapper
 from .hubert_kmeans import HubertWithKmeans
+from .mel_loss import MelSpectrogram, multi_spectral_recon_loss
 from .optimizer import FusedAdam, get_optimizer
 from .resample import resample
 from .soundstream import SoundStream

@@ -181,6 +181,12 @@ SIGNATURES = {
     'alm_modrelu_bwd': [_P, _P, _P, _P, _P, _P, _L, _P],
     'alm_cabs_fwd': [_P, _P, _L, _P],
     'alm_cabs_bwd': [_P, _P, _P, _L, _P],
+    'alm_mel_power_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_mel_project_fwd': [_P, _P, _P, _I, _I, _I, _I, _P],
+    'alm_mel_loss_ws_floats': [],
+    'alm_mel_frame_loss_fwd': [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    'alm_mel_frame_loss_bwd': [_P, _P, _P, _P, _I, _I, _I, _F, _P],
+    'alm_mel_power_bwd': [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     'alm_memset_zero': [_P, _L, _P],
     'alm_list_op_id': [ctypes.c_char_p],
     'alm_list_op_nargs': [_I],

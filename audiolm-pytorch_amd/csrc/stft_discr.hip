@@ -1,11 +1,10 @@
 // ComplexSTFTDiscriminator of SoundStream training (reference soundstream.py:173-310), fp32.  Complex tensors are interleaved (re, im) pairs, the
 // storage of torch.complex64; every gradient is the pair (dL/dre, dL/dim).  No atomics: every sum has one fixed order.
 //
-// One implicit-GEMM kernel on the exact-fp32 matrix core (v_mfma_f32_32x32x2_f32) carries every matrix product of the module.  A workgroup of 4 waves
-// owns a 64 (M) x 64 (N) tile, each wave a 32 x 32 block; the reduction runs in chunks of 32 through LDS (A [64][32], B [32][64]), the next chunk's
-// global loads in flight while the matrix core works on the current one (the loop of conv_valid_kernel in dense_f32.hip).  What differs between the
-// products is WHERE an operand element lives, so each product is a small functor: a(m, k), b(k, n), store(m, n, v), all bounds-checked by the functor
-// (indices past M / N / K never reach it).
+// One implicit-GEMM kernel on the exact-fp32 matrix core (v_mfma_f32_32x32x2_f32) carries every matrix product of the module: gemm64_kernel of
+// gemm64.hpp (shared with mel_loss.hip), a 64 (M) x 64 (N) tile per workgroup of 4 waves, the loop of conv_valid_kernel in dense_f32.hip.  What differs
+// between the products is WHERE an operand element lives, so each product is a small functor: a(m, k), b(k, n), store(m, n, v) (indices past
+// M / N / K never reach it).
 //   STFT forward   : M = 2 F (f, re | im), N = B T, K = n_fft.  A = the windowed DFT basis [n_fft][2 F] built by the host in float64; B = the frame
 //                    sample, reflect padding done by mirroring the index (no padded copy).
 //   STFT backward  : frames' gradient [n_fft][B T] = basis x dX (M = n_fft, K = 2 F) into a workspace, then every output sample gathers its own sum
@@ -17,88 +16,12 @@
 //                    its P (and, from the tiles of the first column, the row sums = the bias gradient) to its slab of the workspace;
 //                    cconv_wgrad_reduce_kernel adds the slabs in split order: dWr = P(0,0) + P(1,1), dWi = P(1,0) - P(0,1).
 // ModReLU y = relu(|z| + b) z / |z| and |z|: elementwise, b read from device memory; db of ModReLU in two fixed-order stages.
-#include "common.hpp"
+#include "gemm64.hpp"
 #include "../../include/audiolm_hip.h"
 
 namespace {
 
-constexpr int GK = 32;                   // reduction chunk
 constexpr int RED_SPAN = 4096, RED_MAX_BLOCKS = 1024;
-
-// OP: int M, N; k range [k_lo(z), k_hi(z)); float a(m, k), b(k, n); void store(m, n, v, z); void rowsum(m, v, z) when ROWSUM
-template <class OP, bool A_MFAST, bool ROWSUM>
-__global__ __launch_bounds__(256) void gemm64_kernel(OP op) {
-    __shared__ float As[64][GK + 1];
-    __shared__ float Bs[GK][64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lr = lane & 31, lh = lane >> 5, wm = wave >> 1, wn = wave & 1;
-    const int n0 = blockIdx.x * 64, m0 = blockIdx.y * 64, z = blockIdx.z;
-    const int klo = op.k_lo(z), khi = op.k_hi(z);
-    // A: k fastest (k = tid & 31, m = tid >> 5 + 8 i) or m fastest (m = tid & 63, k = tid >> 6 + 4 i);  B: n = tid & 63, k = tid >> 6 + 4 i
-    const int a0 = A_MFAST ? (tid & 63) : (tid & 31), a1 = A_MFAST ? (tid >> 6) : (tid >> 5);
-    const int bn = n0 + (tid & 63), bk = tid >> 6;
-    typename OP::NState ns;
-    const bool nok = bn < op.N;
-    if (nok) op.decode_n(bn, ns);
-    float areg[8], breg[8];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int m = m0 + (A_MFAST ? a0 : a1 + 8 * i), k = k0 + (A_MFAST ? a1 + 4 * i : a0);
-            areg[i] = (m < op.M && k < khi) ? op.a(m, k) : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int k = k0 + bk + 4 * i;
-            breg[i] = (nok && k < khi) ? op.b(k, ns) : 0.f;
-        }
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            if (A_MFAST) As[a0][a1 + 4 * i] = areg[i];
-            else As[a1 + 8 * i][a0] = areg[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) Bs[bk + 4 * i][tid & 63] = breg[i];
-    };
-    f32x16 acc;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-    float rs = 0.f;
-    if (klo < khi) {                                             // uniform over the block
-        load(klo);
-        stage();
-        __syncthreads();
-        for (int k0 = klo; k0 < khi; k0 += GK) {
-            const bool more = k0 + GK < khi;
-            if (more) load(k0 + GK);
-#pragma unroll
-            for (int kk = 0; kk < GK / 2; ++kk)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[wm * 32 + lr][2 * kk + lh], Bs[2 * kk + lh][wn * 32 + lr], acc, 0, 0, 0);
-            if (ROWSUM && blockIdx.x == 0 && tid < 64) {
-                for (int kk = 0; kk < GK; ++kk) rs += As[tid][kk];
-            }
-            __syncthreads();
-            if (more) {
-                stage();
-                __syncthreads();
-            }
-        }
-    }
-    if constexpr (ROWSUM) {
-        if (blockIdx.x == 0 && tid < 64 && m0 + tid < op.M) op.rowsum(m0 + tid, rs, z);
-    }
-    const int n = n0 + wn * 32 + lr;
-    if (n >= op.N) return;
-    typename OP::NState os;
-    op.decode_n(n, os);
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int m = m0 + wm * 32 + (v & 3) + 8 * (v >> 2) + 4 * lh;
-        if (m < op.M) op.store(m, os, acc[v], z);
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ STFT
 
@@ -384,14 +307,6 @@ __global__ __launch_bounds__(256) void cabs_bwd_kernel(const float* __restrict__
     float2 o = {0.f, 0.f};
     if (r > 0.f) o.x = g[i] * (v.x / r), o.y = g[i] * (v.y / r);
     dz[i] = o;
-}
-
-template <class OP, bool A_MFAST, bool ROWSUM>
-int launch_gemm(const OP& op, int splits, hipStream_t st) {
-    const dim3 grid((unsigned)((op.N + 63) / 64), (unsigned)((op.M + 63) / 64), (unsigned)splits);
-    hipLaunchKernelGGL((gemm64_kernel<OP, A_MFAST, ROWSUM>), grid, dim3(256), 0, st, op);
-    ALM_LAUNCH_CHECK();
-    return 0;
 }
 
 bool stft_ok(int B, int n, int n_fft, int hop, int F) { return B > 0 && n > 0 && n_fft > 0 && hop > 0 && F > 0 && F <= n_fft; }

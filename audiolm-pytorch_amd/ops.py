@@ -1817,3 +1817,64 @@ def complex_abs_bwd(g, z):
     dz = _new_like(z)
     _lib.call('alm_cabs_bwd', g.data_ptr(), z.data_ptr(), dz.data_ptr(), g.numel(), _st())
     return dz
+
+
+# ---- multi-spectral mel-spectrogram reconstruction loss of SoundStream training (csrc/mel_loss.hip), fp32, no atomics
+
+def mel_power(x, basis, n_fft, hop_length, k_lo, k_hi, x_from=None):
+    """x fp32 [B, n] -> (P fp32 [B, F, T] = |STFT|^2, X): the DFT product of `stft` over the basis rows [k_lo, k_hi) (the window's support; the rows
+    outside are zeros) with the power formed in its epilogue.  With x_from given, X fp32 [B - x_from, F, T, 2] is the complex spectrum of the batch
+    rows from x_from on (what a backward needs); else None."""
+    assert _chk(x, F32).is_contiguous() and x.ndim == 2 and _chk(basis, F32).is_contiguous() and basis.shape[0] == n_fft and basis.shape[1] % 2 == 0
+    B, n = x.shape
+    T, F = stft_frames(n, n_fft, hop_length), basis.shape[1] // 2
+    if T < 1:
+        raise _lib.AlmError(f'mel_power: a clip of {n} samples is too short for the reflect padding of n_fft = {n_fft} (needs more than n_fft / 2)')
+    P = _new((B, F, T), dtype=F32, device=x.device)
+    X = None if x_from is None else _new((B - x_from, F, T, 2), dtype=F32, device=x.device)
+    _lib.call('alm_mel_power_fwd', x.data_ptr(), basis.data_ptr(), P.data_ptr(), _p(X), B, B if x_from is None else x_from, n, n_fft, hop_length, F,
+              k_lo, k_hi, _st())
+    return P, X
+
+
+def mel_project(P, fb):
+    """P fp32 [B, F, T], fb fp32 [F, n_mels] -> mel fp32 [B, n_mels, T] = fb^T P"""
+    assert _chk(P, F32).is_contiguous() and P.ndim == 3 and _chk(fb, F32).is_contiguous() and fb.ndim == 2 and fb.shape[0] == P.shape[1]
+    B, F, T = P.shape
+    mel = _new((B, fb.shape[1], T), dtype=F32, device=P.device)
+    _lib.call('alm_mel_project_fwd', P.data_ptr(), fb.data_ptr(), mel.data_ptr(), B, F, T, fb.shape[1], _st())
+    return mel
+
+
+def mel_frame_loss(mel, alpha):
+    """mel fp32 [2 Bh, n_mels, T] (first half real, second fake) -> (loss 0-dim = means[0] + alpha means[1], means fp32 [2] = (mean over frames of
+    sum_m |Mo - Mr|, mean of norms), norms fp32 [Bh, T] = per frame ||log max(Mo, 1e-20) - log max(Mr, 1e-20)||_2), summed in two fixed-order stages"""
+    assert _chk(mel, F32).is_contiguous() and mel.ndim == 3 and mel.shape[0] % 2 == 0
+    Bh, n_mels, T = mel.shape[0] // 2, mel.shape[1], mel.shape[2]
+    norms = _new((Bh, T), dtype=F32, device=mel.device)
+    loss = _new((), dtype=F32, device=mel.device)
+    means = _new((2,), dtype=F32, device=mel.device)
+    ws = _new((_lib.query('alm_mel_loss_ws_floats'),), dtype=F32, device=mel.device)
+    _lib.call('alm_mel_frame_loss_fwd', mel.data_ptr(), norms.data_ptr(), loss.data_ptr(), means.data_ptr(), ws.data_ptr(), Bh, n_mels, T, float(alpha), _st())
+    return loss, means, norms
+
+
+def mel_frame_loss_bwd(mel, norms, gout, alpha):
+    """d(gout * loss) / d(fake half of mel) fp32 [Bh, n_mels, T] of mel_frame_loss; gout 0-dim fp32, read on the device"""
+    assert _chk(mel, F32).is_contiguous() and _chk(norms, F32).is_contiguous() and _chk(gout, F32).numel() == 1
+    Bh, n_mels, T = mel.shape[0] // 2, mel.shape[1], mel.shape[2]
+    assert norms.shape == (Bh, T)
+    dmel = _new((Bh, n_mels, T), dtype=F32, device=mel.device)
+    _lib.call('alm_mel_frame_loss_bwd', mel.data_ptr(), norms.data_ptr(), gout.data_ptr(), dmel.data_ptr(), Bh, n_mels, T, float(alpha), _st())
+    return dmel
+
+
+def mel_power_bwd(dmel, fb, X):
+    """dmel fp32 [B, n_mels, T], fb fp32 [F, n_mels], X fp32 [B, F, T, 2] -> dX fp32 [B, F, T, 2] = 2 X (fb dmel), the operand of stft_bwd"""
+    assert all(_chk(t, F32).is_contiguous() for t in (dmel, fb, X))
+    B, n_mels, T = dmel.shape
+    F = fb.shape[0]
+    assert fb.shape == (F, n_mels) and X.shape == (B, F, T, 2), (tuple(dmel.shape), tuple(fb.shape), tuple(X.shape))
+    dX = _new_like(X)
+    _lib.call('alm_mel_power_bwd', dmel.data_ptr(), fb.data_ptr(), X.data_ptr(), dX.data_ptr(), B, F, T, n_mels, _st())
+    return dX

@@ -4,8 +4,8 @@ return_codes_only=True)` -- the causal-conv encoder (soundstream.py:332-380, 519
 (soundstream.py:592-607, :840) -- and `decode_from_codebook_indices` / `decode` (soundstream.py:691-709: code lookup, transposed-conv
 decoder :347-360, 382-395, 615-627) run on the MI355X kernels of csrc/codec.hip (exact-fp32 MFMA).  The training losses (soundstream.py:868-995:
 three wave MultiScaleDiscriminators, hinge / feature / reconstruction terms) are opt-in, `with_discriminators=True` (discriminators.py,
-csrc/discr.hip), and so is the ComplexSTFTDiscriminator, `stft_discriminator=True` (csrc/stft_discr.hip); the mel-spectrogram loss, the gradient
-penalty and the LFQ / FSQ quantizers are out of scope and raise.  In training mode the quantizer takes one
+csrc/discr.hip), and so are the ComplexSTFTDiscriminator, `stft_discriminator=True` (csrc/stft_discr.hip), and the multi-spectral mel-spectrogram
+reconstruction loss, `with_mel_loss=True` (mel_loss.py, csrc/mel_loss.hip); the gradient penalty and the LFQ / FSQ quantizers are out of scope and raise.  In training mode the quantizer takes one
 training step per call (csrc/rvq_train.hip: quantize dropout, commitment loss, rotation trick, EMA codebooks with dead-code expiry, k-means
 initialisation; single process only), so `forward(x, return_recons_only=True | return_encoded=True)` is differentiable end to end.  The conv encoder / decoder are
 differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
@@ -36,7 +36,7 @@ from itertools import cycle
 import torch
 from torch import nn
 
-from . import codec_bwd, core, discriminators as D, ops
+from . import codec_bwd, core, discriminators as D, mel_loss, ops
 from .resample import resample
 
 F32 = torch.float32
@@ -547,7 +547,8 @@ class SoundStream(nn.Module):
                  feature_loss_weight=100, target_sample_hz=16000, use_local_attn=True, attn_window_size=128, attn_dim_head=64, attn_heads=8, attn_depth=1,
                  attn_xpos_scale_base=None, attn_dynamic_pos_bias=False, use_gate_loop_layers=False, squeeze_excite=False, pad_mode='reflect',
                  stft_discriminator=None, with_discriminators=False, stft_normalized=False, complex_stft_discr_logits_abs=True,
-                 complex_stft_discr_kwargs: dict = {}, **kwargs):
+                 complex_stft_discr_kwargs: dict = {}, with_mel_loss=False, multi_spectral_window_powers_of_two=tuple(range(6, 12)),
+                 multi_spectral_n_ffts=512, multi_spectral_n_mels=64, **kwargs):
         super().__init__()
         if use_lookup_free_quantizer or use_finite_scalar_quantizer or finite_scalar_quantizer_levels is not None:
             raise NotImplementedError('LFQ / FSQ quantizers are out of scope (SURVEY.md §2)')
@@ -599,6 +600,24 @@ class SoundStream(nn.Module):
             elif stft_discriminator not in (None, False):
                 raise TypeError('stft_discriminator: True (the native ComplexSTFTDiscriminator), an nn.Module with '
                                 'forward(x, return_intermediates=False), False (train without one) or None')
+        # the multi-spectral mel reconstruction loss (soundstream.py:645-672) is opt-in on top: without `with_mel_loss=True` nothing is registered,
+        # the multi_spectral_* keywords are ignored and a positive weight makes the loss branches raise, like before
+        self.with_mel_loss = bool(with_mel_loss)
+        if self.with_mel_loss:
+            if not self.with_discriminators:
+                raise ValueError('with_mel_loss=True needs with_discriminators=True (the mel term is part of the generator loss)')
+            powers = tuple(multi_spectral_window_powers_of_two)
+            cast = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v,) * len(powers)
+            n_ffts, n_mels = cast(multi_spectral_n_ffts), cast(multi_spectral_n_mels)
+            if not len(n_ffts) == len(n_mels) == len(powers):
+                raise ValueError('multi_spectral_n_ffts / multi_spectral_n_mels: one value, or one per entry of multi_spectral_window_powers_of_two')
+            self.mel_spec_transforms = nn.ModuleList([])
+            self.mel_spec_recon_alphas = []
+            for power, n_fft, mels in zip(powers, n_ffts, n_mels):
+                win_length = 2 ** power
+                self.mel_spec_transforms.append(mel_loss.MelSpectrogram(sample_rate=target_sample_hz, n_fft=max(n_fft, win_length), win_length=win_length,
+                                                                        hop_length=win_length // 4, n_mels=mels, normalized=stft_normalized))
+                self.mel_spec_recon_alphas.append((win_length / 2) ** 0.5)
         self.eval()
 
     @property
@@ -669,6 +688,9 @@ class SoundStream(nn.Module):
             self._check_loss_options(apply_grad_penalty)
         with torch.set_grad_enabled(torch.is_grad_enabled() and self.training):
             x, lead = self.process_input(x, input_sample_hz=input_sample_hz, curtail_from_left=curtail_from_left)
+            if self._mel_term_on() and not codec_only and not return_discr_loss:
+                for transform in self.mel_spec_transforms:       # a clip too short for a scale's reflect padding: by name, before the codec's launches
+                    transform.check_length(x.shape[-1])
             feats = self.encode(x)
             quantized, indices, commit_loss = self.rq(feats)
             if return_codes_only:
@@ -687,10 +709,10 @@ class SoundStream(nn.Module):
             return self._generator_loss(orig_x, recon, orig_x if target is None else target.to(F32).contiguous(), commit_loss, return_loss_breakdown)
 
     def _check_loss_options(self, apply_grad_penalty):
-        """the three parts of the reference's losses that are not built, each by name, before any launch"""
-        if self.multi_spectral_recon_loss_weight > 0:
-            raise NotImplementedError('the multi-spectral mel-spectrogram reconstruction loss (torchaudio MelSpectrogram) is not implemented: construct '
-                                      'the SoundStream with multi_spectral_recon_loss_weight=0')
+        """the parts of the reference's losses that are not built, each by name, before any launch"""
+        if self.multi_spectral_recon_loss_weight > 0 and not self.with_mel_loss:
+            raise NotImplementedError('the multi-spectral mel-spectrogram reconstruction loss (torchaudio MelSpectrogram) is not constructed by default: '
+                                      'pass with_mel_loss=True for the native one, or construct the SoundStream with multi_spectral_recon_loss_weight=0')
         if apply_grad_penalty:
             raise NotImplementedError('apply_grad_penalty=True (gradient penalty) needs a double backward through the discriminator kernels, which is '
                                       'not implemented')
@@ -698,6 +720,9 @@ class SoundStream(nn.Module):
             raise NotImplementedError('the ComplexSTFTDiscriminator is not constructed by default: pass stft_discriminator=True for the native one, '
                                       'stft_discriminator=<an nn.Module with forward(x, return_intermediates=False)>, or stft_discriminator=False '
                                       'to train without one')
+
+    def _mel_term_on(self):
+        return self.with_mel_loss and self.multi_spectral_recon_loss_weight > 0
 
     def _scales(self, real, fake):
         """per wave discriminator (logits, intermediates) of real and fake run as ONE batch [real | fake] through the chain of downsamples"""
@@ -739,7 +764,10 @@ class SoundStream(nn.Module):
 
     def _generator_loss(self, real, fake, target, commit_loss, breakdown):      # soundstream.py:927-995
         recon_loss = D.mse_loss(target, fake)
-        multi_spectral_recon_loss = torch.zeros((), dtype=F32, device=real.device)
+        if self._mel_term_on():                                  # soundstream.py:937-945: from (orig_x, recon_x), never from `target`
+            multi_spectral_recon_loss = mel_loss.multi_spectral_recon_loss(real, fake, self.mel_spec_transforms, self.mel_spec_recon_alphas)
+        else:
+            multi_spectral_recon_loss = torch.zeros((), dtype=F32, device=real.device)
         adversarial, pairs = [], []
         stft_fake_logits = None
         if not self._stft_discriminator_off:

@@ -639,6 +639,28 @@ int alm_modrelu_bwd(const float* g, const float* z, const float* b, float* dz, f
 int alm_cabs_fwd(const float* z, float* y, long long n, void* stream);
 int alm_cabs_bwd(const float* g, const float* z, float* dz, long long n, void* stream);
 
+/* ---- multi-spectral mel-spectrogram reconstruction loss of SoundStream training (csrc/mel_loss.hip), fp32, no atomics ---------------------------------
+ * torchaudio.transforms.MelSpectrogram (power 2, center, reflect, one-sided, HTK) per scale and the two per-frame norms of reference
+ * soundstream.py:933-945; real and fake waves run as one batch [real | fake].  Every matrix product is on the exact-fp32 matrix core.
+ * alm_mel_power_fwd : x [B][n] -> P [B][F][T] = |STFT|^2 (T = alm_stft_frames), the DFT product of alm_stft_fwd with the power formed in its epilogue.
+ *     basis [n_fft][2 F] as for alm_stft_fwd (torchaudio's normalized=True, 1 / sqrt(sum w^2), multiplied in by the host); the reduction runs over the
+ *     basis rows [k_lo, k_hi) only (the window's support; the rows outside must be zeros).  X (may be null) receives the complex spectrum
+ *     [B - x_from][F][T][2] of the batch rows from x_from on.
+ * alm_mel_project_fwd : mel [B][n_mels][T] = fb^T P, fb [F][n_mels].
+ * alm_mel_frame_loss_fwd : mel [2 Bh][n_mels][T] (first half real, second fake) -> norms [Bh T] = per frame ||log max(Mo, 1e-20) - log max(Mr, 1e-20)||_2,
+ *     means[0] = mean over frames of sum_m |Mo - Mr|, means[1] = mean of norms, loss[0] = means[0] + alpha means[1]; two fixed-order stages through ws
+ *     (alm_mel_loss_ws_floats floats).
+ * alm_mel_frame_loss_bwd : dmel [Bh][n_mels][T] = d(gout loss) / d(fake mel), gout a scalar in device memory; sign(0) = 0, 0 through an inactive clamp
+ *     and where a frame's norm is 0.
+ * alm_mel_power_bwd : dX [B][F][T][2] = 2 X (fb dmel): the gradient of the spectrum X [B][F][T][2], the operand of alm_stft_bwd. */
+int alm_mel_power_fwd(const float* x, const float* basis, float* P, float* X, int B, int x_from, int n, int n_fft, int hop, int F, int k_lo, int k_hi,
+                      void* stream);
+int alm_mel_project_fwd(const float* P, const float* fb, float* mel, int B, int F, int T, int n_mels, void* stream);
+int alm_mel_loss_ws_floats(void);
+int alm_mel_frame_loss_fwd(const float* mel, float* norms, float* loss, float* means, float* ws, int Bh, int n_mels, int T, float alpha, void* stream);
+int alm_mel_frame_loss_bwd(const float* mel, const float* norms, const float* gout, float* dmel, int Bh, int n_mels, int T, float alpha, void* stream);
+int alm_mel_power_bwd(const float* dmel, const float* fb, const float* X, float* dX, int B, int F, int T, int n_mels, void* stream);
+
 /* ---- launch lists (round 6): a recorded sequence of the launches above re-issued by ONE host call ---------------------------------------------
  * The depth loop of audiolm_pytorch.py:528-547 (Transformer.forward) and its backward are ~190 launches per training step whose ORDER and scalar arguments
  * depend only on the model configuration and the batch shape; only buffer addresses change between steps.  The host records the sequence once per shape

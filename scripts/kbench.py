@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss]"""
 import os
 import sys
 import time
@@ -852,6 +852,71 @@ def bench_stft_discr():
             if name.endswith('0.fn.0'):                          # the unit's second 3 x 3 conv has the first one's form: step over it
                 with torch.no_grad():
                     h = hin.detach()
+
+
+def bench_mel_loss():
+    """Multi-spectral mel reconstruction loss of SoundStream training at 8 x 1 s and 8 x 3 s of 16 kHz audio: forward + backward (d / d recon) of the
+    six-scale term at the reference defaults on the kernels of csrc/mel_loss.hip, against the SAME computation issued through PyTorch-ROCm
+    (tests/mel_restated.py moved to the GPU: torch.stft + matmul + autograd, fp32) on the same box; then every scale alone, and the native launches of
+    each scale one by one.  Interleaved rounds, medians, one event pair per call."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    from mel_restated import MelSpectrogramRestated, multi_spectral_recon_loss_restated
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def median(fns, rounds=10, warm=3):
+        for _ in range(warm):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(rounds):
+            for t, fn in zip(ts, fns):
+                t.append(once(fn))
+        return [sorted(t)[len(t) // 2] for t in ts]
+
+    ours, refs, alphas = [], [], []
+    for p in range(6, 12):
+        win = 2 ** p
+        kw = dict(sample_rate=16000, n_fft=max(512, win), win_length=win, hop_length=win // 4, n_mels=64, normalized=False)
+        ours.append(A.MelSpectrogram(**kw).to(dev))
+        refs.append(MelSpectrogramRestated(**kw).float().to(dev))
+        alphas.append((win / 2) ** 0.5)
+
+    def hand(ts, al, orig, recon):
+        torch.autograd.grad(A.multi_spectral_recon_loss(orig, recon, ts, al), [recon])
+
+    def aten(ts, al, orig, recon):
+        torch.autograd.grad(multi_spectral_recon_loss_restated(orig, recon, ts, al), [recon])
+
+    for secs in (1, 3):
+        n = 16000 * secs
+        orig, recon = torch.randn(8, 1, n, device=dev) * 0.3, (torch.randn(8, 1, n, device=dev) * 0.3).requires_grad_()
+        t_o, t_a = median([lambda: hand(ours, alphas, orig, recon), lambda: aten(refs, alphas, orig, recon)])
+        print(f'mel_loss 8 x {secs} s: six-scale term fwd + bwd: hand {t_o:.3f} ms   ATen {t_a:.3f} ms   hand / ATen {t_o / t_a:.2f}   '
+              '(per scale: 4 launches forward, 4 backward)', flush=True)
+        both = torch.cat((orig, recon.detach())).reshape(16, n)
+        g = torch.ones((), device=dev)
+        for t, r, alpha in zip(ours, refs, alphas):
+            t_o, t_a = median([lambda: hand([t], [alpha], orig, recon), lambda: aten([r], [alpha], orig, recon)])
+            basis, fb, left = t._dft_basis(dev), t.mel_scale.fb, (t.n_fft - t.win_length) // 2
+            P, X = ops.mel_power(both, basis, t.n_fft, t.hop_length, left, left + t.win_length, x_from=8)
+            mel = ops.mel_project(P, fb)
+            _, _, norms = ops.mel_frame_loss(mel, alpha)
+            dmel = ops.mel_frame_loss_bwd(mel, norms, g, alpha)
+            dX = ops.mel_power_bwd(dmel, fb, X)
+            parts = median([lambda: ops.mel_power(both, basis, t.n_fft, t.hop_length, left, left + t.win_length, x_from=8), lambda: ops.mel_project(P, fb),
+                            lambda: ops.mel_frame_loss(mel, alpha), lambda: ops.mel_frame_loss_bwd(mel, norms, g, alpha),
+                            lambda: ops.mel_power_bwd(dmel, fb, X), lambda: ops.stft_bwd(dX, basis, n, t.n_fft, t.hop_length)])
+            names = ('power', 'project', 'frame loss (2)', 'column grad', 'dP -> dX', 'stft bwd (2)')
+            print(f'    win {t.win_length:4d} n_fft {t.n_fft:4d} hop {t.hop_length:3d} T {mel.shape[-1]:5d}: hand {t_o:.3f} ms   ATen {t_a:.3f} ms   hand / ATen '
+                  f'{t_o / t_a:.2f}   launches: ' + ', '.join(f'{k} {v * 1e3:.0f} us' for k, v in zip(names, parts)), flush=True)
 
 
 if __name__ == '__main__':
