@@ -146,7 +146,7 @@ int rows_grid(long long rows) { const long long g = (rows + 3) / 4; return (int)
 extern "C" int alm_xattn_softmax_fwd(const float* S, long long ldS, const unsigned char* emask, const float* lse_self, float scale, void* P,
                                      long long ldP, float* lse_tot, float* fself, const float* bias, long long ldbias, int causal_off, int B, int N,
                                      int H, int Me, void* stream) {
-    if (Me < 1 || ldS < Me || ldP < Me || !S || !P || !lse_tot || (bias && ldbias < Me)) return ALM_ERR_BAD_ARG;
+    if (!S || !P || !lse_tot || B < 1 || N < 1 || H < 1 || Me < 1 || ldS < Me || ldP < Me || (bias && ldbias < Me)) return ALM_ERR_BAD_ARG;
     hipLaunchKernelGGL(extra_softmax_fwd_kernel, dim3(rows_grid((long long)B * N * H)), dim3(256), 0, (hipStream_t)stream, S, ldS, emask, lse_self,
                        scale, (bf16_t*)P, ldP, lse_tot, fself, bias, ldbias, causal_off, B, N, H, Me);
     ALM_LAUNCH_CHECK();
@@ -155,7 +155,8 @@ extern "C" int alm_xattn_softmax_fwd(const float* S, long long ldS, const unsign
 
 extern "C" int alm_xattn_combine(const void* o_self, long long ldos, const float* fself, const float* o_e, void* out, long long ldo, long long tokens,
                                  int H, int dim_head, void* stream) {
-    if ((dim_head & 3) || (ldo & 3) || (o_self && ((ldos & 3) || !fself))) return ALM_ERR_BAD_ARG;
+    if (!o_e || !out || tokens < 1 || H < 1 || dim_head < 1 || (dim_head & 3) || (ldo & 3) || ldo < (long long)H * dim_head) return ALM_ERR_BAD_ARG;
+    if (o_self && (!fself || (ldos & 3) || ldos < (long long)H * dim_head)) return ALM_ERR_BAD_ARG;
     const long long total = tokens * H * (dim_head / 4);
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
     hipLaunchKernelGGL(attn_combine_kernel, dim3(grid < 1 ? 1 : grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)o_self, ldos, fself, o_e,
@@ -166,7 +167,7 @@ extern "C" int alm_xattn_combine(const void* o_self, long long ldos, const float
 
 extern "C" int alm_xattn_softmax_bwd(const void* P, long long ldP, const float* dP, long long lddP, const float* ndelta, float scale, void* dS,
                                      long long lddS, int Me, int B, int N, int H, void* stream) {
-    if (lddP < ldP || lddS < ldP || Me > ldP) return ALM_ERR_BAD_ARG;
+    if (!P || !dP || !ndelta || !dS || B < 1 || N < 1 || H < 1 || Me < 1 || Me > ldP || lddP < ldP || lddS < ldP) return ALM_ERR_BAD_ARG;
     hipLaunchKernelGGL(extra_softmax_bwd_kernel, dim3(rows_grid((long long)B * N * H)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)P, ldP, dP,
                        lddP, ndelta, scale, (bf16_t*)dS, lddS, Me, B, N, H);
     ALM_LAUNCH_CHECK();
@@ -175,6 +176,8 @@ extern "C" int alm_xattn_softmax_bwd(const void* P, long long ldP, const float* 
 
 extern "C" int alm_xattn_delta(const void* o, long long ldo, const void* dout, long long lddo, float* ndelta, int B, int N, int H, int dim_head,
                                void* stream) {
+    if (!o || !dout || !ndelta || B < 1 || N < 1 || H < 1 || dim_head < 1) return ALM_ERR_BAD_ARG;
+    if (ldo < (long long)H * dim_head || lddo < (long long)H * dim_head) return ALM_ERR_BAD_ARG;
     hipLaunchKernelGGL(xattn_delta_kernel, dim3(rows_grid((long long)B * N * H)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)o, ldo,
                        (const bf16_t*)dout, lddo, ndelta, B, N, H, dim_head);
     ALM_LAUNCH_CHECK();
@@ -183,7 +186,7 @@ extern "C" int alm_xattn_delta(const void* o, long long ldo, const void* dout, l
 
 extern "C" int alm_xattn_dbias(const void* P, long long ldP, const float* dP, long long lddP, const float* ndelta, float* dbias, long long lddb,
                                int Me, int B, int N, int H, void* stream) {
-    if (Me < 1 || ldP < Me || lddP < Me || lddb < Me) return ALM_ERR_BAD_ARG;
+    if (!P || !dP || !ndelta || !dbias || B < 1 || N < 1 || H < 1 || Me < 1 || ldP < Me || lddP < Me || lddb < Me) return ALM_ERR_BAD_ARG;
     hipLaunchKernelGGL(xattn_dbias_kernel, dim3(rows_grid((long long)N * H)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)P, ldP, dP, lddP, ndelta,
                        dbias, lddb, Me, B, N, H);
     ALM_LAUNCH_CHECK();
