@@ -17,7 +17,7 @@ _lib.load()            # no fallback path exists: fail at import, loudly, if lib
 from .attend import Attend  # noqa: E402
 from .audiolm_pytorch import (AudioLM, CoarseTransformer, CoarseTransformerWrapper, FineTransformer, FineTransformerWrapper,
                               SemanticTransformer, SemanticTransformerWrapper, Transformer, get_embeds)
-from .discriminators import ComplexSTFTDiscriminator, MultiScaleDiscriminator
+from .discriminators import ComplexSTFTDiscriminator, MultiScaleDiscriminator, gradient_penalty
 from .encodec import EncodecWrapper
 from .hubert_kmeans import HubertWithKmeans
 from .mel_loss import MelSpectrogram, multi_spectral_recon_loss

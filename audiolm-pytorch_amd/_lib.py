@@ -159,6 +159,7 @@ SIGNATURES = {
     'alm_gconv1d_out_len': [_I, _I, _I, _I],
     'alm_gconv1d_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'alm_gconv1d_dgrad': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'alm_gconv1d_fwd_masked': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'alm_gconv1d_wgrad_ws_floats': [_I, _I, _I, _I, _I, _I, _I, _I],
     'alm_gconv1d_wgrad': [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'alm_avgpool1d_out_len': [_I, _I],
@@ -167,6 +168,9 @@ SIGNATURES = {
     'alm_loss_ws_floats': [],
     'alm_loss_mean_fwd': [_P, _P, _P, _P, _L, _I, _P],
     'alm_loss_mean_bwd': [_P, _P, _P, _P, _P, _L, _I, _P],
+    'alm_grad_penalty_ws_floats': [_I, _L],
+    'alm_grad_penalty_fwd': [_P, _P, _P, _P, _L, _I, _L, _F, _F, _P],
+    'alm_grad_penalty_bwd': [_P, _P, _P, _P, _I, _L, _F, _F, _P],
     'alm_stft_frames': [_I, _I, _I],
     'alm_stft_fwd': [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     'alm_stft_bwd_ws_floats': [_I, _I, _I, _I],
@@ -181,6 +185,8 @@ SIGNATURES = {
     'alm_modrelu_bwd': [_P, _P, _P, _P, _P, _P, _L, _P],
     'alm_cabs_fwd': [_P, _P, _L, _P],
     'alm_cabs_bwd': [_P, _P, _P, _L, _P],
+    'alm_modrelu_bwd2': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    'alm_cabs_bwd2': [_P, _P, _P, _P, _P, _L, _P],
     'alm_mel_power_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'alm_mel_project_fwd': [_P, _P, _P, _I, _I, _I, _I, _P],
     'alm_mel_loss_ws_floats': [],

@@ -12,10 +12,14 @@
 //             Cout_t x Cin_t x k sums in registers over ALL chunks of its split (walked in list order), writes them to the split's slab of the workspace,
 //             and discr_wgrad_reduce_kernel adds the slabs in split order.  The split count depends on the shapes only: gradients are bitwise reproducible.
 // The activation's derivative comes from the saved OUTPUT (y > 0 <=> pre-activation > 0), like the ELU path of codec_bwd.hip.
+//   masked  : the forward tiling with another epilogue, out = m(y) conv(v, w) without a bias, m(y) = 1 where the saved output y > 0 and 0.1 elsewhere
+//             (y null: m = 1).  It is the derivative of dgrad with respect to its incoming gradient: the double backward of the gradient penalty.
 //
 // AvgPool1d(2 f, stride f, padding f), count_include_pad: y[t] = sum_{i < 2f} x[t f - f + i] / (2 f); its adjoint gathers the <= 2 windows over u.
 // Loss reductions (hinge discriminator / hinge generator / L1 / squared error / complex L1 = mean modulus means): per-block partial sums over a contiguous span in a fixed lane
 // order, then one block adds the partials in index order; the backward is elementwise and takes the upstream gradient from device memory.
+// Gradient penalty (soundstream.py:70-83) weight / R sum_r (|G_r| - center)^2 of G [R][n]: the rows' sums of squares the same way (per-block spans of a
+// row, partials added in index order), the R norms kept for the elementwise backward.
 #include "common.hpp"
 #include "../../include/audiolm_hip.h"
 
@@ -26,15 +30,16 @@ constexpr int XS_MAX = 6144;             // floats of the staged signal window
 constexpr int WS_MAX = 4096;             // floats of the staged weights
 constexpr int WG_ACC = 12;               // sums per thread of the weight gradient
 constexpr float LEAK = 0.1f;
+constexpr int ACT_MASKED = 2;            // forward epilogue of the masked form: no bias, times m(y)
 
 struct GConvArgs {
     const float* x;      // forward: input [B][Cin][Tin]; dgrad: unused; wgrad: input
     const float* w;      // [Cout][cig][K]
     const float* bias;   // [Cout] (forward)
     const float* g;      // dL/dy [B][Cout][Tout] (backward)
-    const float* y;      // saved output (backward, act) or null
+    const float* y;      // saved output (backward, act; masked forward) or null
     float* out;          // forward: y; dgrad: dx; wgrad: workspace
-    int B, Cin, Cout, Tin, Tout, K, s, p, G, cig, cog, act;
+    int B, Cin, Cout, Tin, Tout, K, s, p, G, cig, cog, act;      // forward act: 0 identity, 1 LeakyReLU, ACT_MASKED
     int chunk;           // reduce channels staged per round (forward: input, dgrad: output channels)
     int row;             // floats per staged signal row
     int tiles;           // channel tiles per group (forward: of cog, dgrad: of cig)
@@ -90,9 +95,16 @@ __global__ __launch_bounds__(256) void gconv_fwd_kernel(GConvArgs a) {
             const int co = co0 + cl * J + j;
             if (co < a.cog) {
                 const int cg = grp * a.cog + co;
-                float v = acc[j] + a.bias[cg];
-                if (a.act) v = v > 0.f ? v : LEAK * v;
-                a.out[((size_t)b * a.Cout + cg) * a.Tout + t] = v;
+                const size_t o = ((size_t)b * a.Cout + cg) * a.Tout + t;
+                float v;
+                if (a.act == ACT_MASKED) {
+                    v = acc[j];
+                    if (a.y && !(a.y[o] > 0.f)) v *= LEAK;
+                } else {
+                    v = acc[j] + a.bias[cg];
+                    if (a.act) v = v > 0.f ? v : LEAK * v;
+                }
+                a.out[o] = v;
             }
         }
     }
@@ -355,6 +367,71 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
     if (db) db[i] = gb;
 }
 
+// ------------------------------------------------------------------------------------------------ gradient penalty
+
+// grid (nparts, R): this block's span of row r, squares summed in a fixed lane order, into part[r][blockIdx.x]
+__global__ __launch_bounds__(256) void penalty_partial_kernel(const float* __restrict__ G, float* __restrict__ part, long long n, long long span) {
+    const long long lo = (long long)blockIdx.x * span, hi = min(n, lo + span);
+    const float* row = G + (size_t)blockIdx.y * n;
+    float s = 0.f;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) s = fmaf(row[i], row[i], s);
+    s = block_sum(s);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// one block: the rows in order, each row's partials in index order; norms[r] = |G_r|, out = scale * sum_r (|G_r| - center)^2
+__global__ __launch_bounds__(256) void penalty_final_kernel(const float* __restrict__ part, float* __restrict__ norms, float* __restrict__ out, int R,
+                                                            int nparts, float scale, float center) {
+    float total = 0.f;
+    for (int r = 0; r < R; ++r) {
+        float s = 0.f;
+        for (int i = threadIdx.x; i < nparts; i += 256) s += part[(size_t)r * nparts + i];
+        s = block_sum(s);
+        const float nr = sqrtf(s), d = nr - center;
+        total = fmaf(d, d, total);
+        if (threadIdx.x == 0) norms[r] = nr;
+    }
+    if (threadIdx.x == 0) out[0] = total * scale;
+}
+
+// dG[r][i] = gout * scale * 2 (|G_r| - center) * G[r][i] / |G_r|, 0 for a row of norm 0
+__global__ __launch_bounds__(256) void penalty_bwd_kernel(const float* __restrict__ G, const float* __restrict__ norms, const float* __restrict__ gout,
+                                                          float* __restrict__ dG, long long n, float scale, float center) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float nr = norms[blockIdx.y];
+    const size_t o = (size_t)blockIdx.y * n + i;
+    dG[o] = nr > 0.f ? gout[0] * scale * 2.f * (nr - center) * (G[o] / nr) : 0.f;
+}
+
+constexpr int PEN_MAX_ROWS = 65535;
+
+// span of a row per block and the blocks per row of the penalty's first stage
+int penalty_parts(long long n, long long& span) {
+    span = RED_SPAN;
+    while ((n + span - 1) / span > RED_MAX_BLOCKS) span *= 2;
+    return (int)((n + span - 1) / span);
+}
+
+int gconv_fwd_launch(GConvArgs& a, hipStream_t stream) {
+    a.Tout = alm_gconv1d_out_len(a.Tin, a.K, a.s, a.p);
+    a.cig = a.Cin / a.G, a.cog = a.Cout / a.G;
+    const int J = a.cog > 4 ? 4 : 1, CT = 4 * J;
+    const long long W = (long long)(TT - 1) * a.s + a.K;
+    const long long row = (W + a.s - 1) / a.s * a.s;
+    if (row > XS_MAX || (long long)CT * a.K > WS_MAX || (long long)a.Tin * a.s >= 0x3fffffffLL) return ALM_ERR_UNSUPPORTED;
+    a.row = (int)row;
+    a.chunk = (int)min((long long)a.cig, min(XS_MAX / row, (long long)WS_MAX / (CT * a.K)));
+    a.tiles = (a.cog + CT - 1) / CT;
+    const long long gy = (long long)a.G * a.tiles;
+    if (gy > 65535 || a.B > 65535) return ALM_ERR_UNSUPPORTED;
+    const dim3 grid((a.Tout + TT - 1) / TT, (unsigned)gy, a.B);
+    if (J == 4) hipLaunchKernelGGL(gconv_fwd_kernel<4>, grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(gconv_fwd_kernel<1>, grid, dim3(256), 0, stream, a);
+    ALM_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int alm_gconv1d_out_len(int Tin, int ksize, int stride, int padding) {
@@ -368,22 +445,17 @@ extern "C" int alm_gconv1d_fwd(const float* x, const float* w, const float* bias
     GConvArgs a = {};
     a.x = x, a.w = w, a.bias = bias, a.out = y;
     a.B = B, a.Cin = Cin, a.Cout = Cout, a.Tin = Tin, a.K = ksize, a.s = stride, a.p = padding, a.G = groups, a.act = act;
-    a.Tout = alm_gconv1d_out_len(Tin, ksize, stride, padding);
-    a.cig = Cin / groups, a.cog = Cout / groups;
-    const int J = a.cog > 4 ? 4 : 1, CT = 4 * J;
-    const long long W = (long long)(TT - 1) * stride + ksize;
-    const long long row = (W + stride - 1) / stride * stride;
-    if (row > XS_MAX || (long long)CT * ksize > WS_MAX || (long long)Tin * stride >= 0x3fffffffLL) return ALM_ERR_UNSUPPORTED;
-    a.row = (int)row;
-    a.chunk = (int)min((long long)a.cig, min(XS_MAX / row, (long long)WS_MAX / (CT * ksize)));
-    a.tiles = (a.cog + CT - 1) / CT;
-    const long long gy = (long long)groups * a.tiles;
-    if (gy > 65535 || B > 65535) return ALM_ERR_UNSUPPORTED;
-    const dim3 grid((a.Tout + TT - 1) / TT, (unsigned)gy, B);
-    if (J == 4) hipLaunchKernelGGL(gconv_fwd_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(gconv_fwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    ALM_LAUNCH_CHECK();
-    return 0;
+    return gconv_fwd_launch(a, (hipStream_t)stream);
+}
+
+// out = m(y) conv1d(v, w) without a bias: the derivative of alm_gconv1d_dgrad(g, y, w) with respect to g, applied to v.  y null: no mask.
+extern "C" int alm_gconv1d_fwd_masked(const float* v, const float* w, const float* y, float* out, int B, int Cin, int Cout, int Tin, int ksize, int stride,
+                                      int padding, int groups, void* stream) {
+    if (v == nullptr || w == nullptr || out == nullptr || !conv_shape_ok(B, Cin, Cout, Tin, ksize, stride, padding, groups)) return ALM_ERR_BAD_ARG;
+    GConvArgs a = {};
+    a.x = v, a.w = w, a.y = y, a.out = out;
+    a.B = B, a.Cin = Cin, a.Cout = Cout, a.Tin = Tin, a.K = ksize, a.s = stride, a.p = padding, a.G = groups, a.act = ACT_MASKED;
+    return gconv_fwd_launch(a, (hipStream_t)stream);
 }
 
 extern "C" int alm_gconv1d_dgrad(const float* g, const float* y, const float* w, float* dx, int B, int Cin, int Cout, int Tin, int ksize, int stride,
@@ -487,6 +559,38 @@ extern "C" int alm_loss_mean_bwd(const float* a, const float* b, const float* go
     if ((n + 255) / 256 >= 0x7fffffffLL) return ALM_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, gout, da, db, n,
                        (float)(1.0 / (double)n), mode);
+    ALM_LAUNCH_CHECK();
+    return 0;
+}
+
+// floats of the caller-owned workspace of alm_grad_penalty_fwd: R rows x the blocks per row; -1 outside the kernel's envelope
+extern "C" int alm_grad_penalty_ws_floats(int R, long long n) {
+    if (R <= 0 || R > PEN_MAX_ROWS || n <= 0) return -1;
+    long long span;
+    return R * penalty_parts(n, span);
+}
+
+extern "C" int alm_grad_penalty_fwd(const float* G, float* out, float* norms, float* ws, long long ws_floats, int R, long long n, float weight,
+                                    float center, void* stream) {
+    if (G == nullptr || out == nullptr || norms == nullptr || ws == nullptr || R <= 0 || n <= 0) return ALM_ERR_BAD_ARG;
+    if (R > PEN_MAX_ROWS) return ALM_ERR_UNSUPPORTED;
+    long long span;
+    const int nparts = penalty_parts(n, span);
+    if (ws_floats < (long long)R * nparts) return ALM_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(penalty_partial_kernel, dim3(nparts, R), dim3(256), 0, st, G, ws, n, span);
+    ALM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(penalty_final_kernel, dim3(1), dim3(256), 0, st, ws, norms, out, R, nparts, (float)((double)weight / (double)R), center);
+    ALM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int alm_grad_penalty_bwd(const float* G, const float* norms, const float* gout, float* dG, int R, long long n, float weight, float center,
+                                    void* stream) {
+    if (G == nullptr || norms == nullptr || gout == nullptr || dG == nullptr || R <= 0 || n <= 0) return ALM_ERR_BAD_ARG;
+    if (R > PEN_MAX_ROWS || (n + 255) / 256 >= 0x7fffffffLL) return ALM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(penalty_bwd_kernel, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, (hipStream_t)stream, G, norms, gout, dG, n,
+                       (float)((double)weight / (double)R), center);
     ALM_LAUNCH_CHECK();
     return 0;
 }

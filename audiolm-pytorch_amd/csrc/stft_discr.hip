@@ -16,6 +16,8 @@
 //                    its P (and, from the tiles of the first column, the row sums = the bias gradient) to its slab of the workspace;
 //                    cconv_wgrad_reduce_kernel adds the slabs in split order: dWr = P(0,0) + P(1,1), dWi = P(1,0) - P(0,1).
 // ModReLU y = relu(|z| + b) z / |z| and |z|: elementwise, b read from device memory; db of ModReLU in two fixed-order stages.
+// Second order (the double backward of the gradient penalty): the backward passes of ModReLU and |z| as functions of (g, z, b), differentiated once
+// more against the cotangents (v, beta) of (dz, db) -- elementwise again, the scalar d/db reduced like db.
 #include "gemm64.hpp"
 #include "../../include/audiolm_hip.h"
 
@@ -107,7 +109,7 @@ struct CConvFwdOp {
     }
     __device__ void store(int m, const NState& s, float v, int) const {
         const size_t o = (s.out + (size_t)(m >> 1) * g.Ho * g.Wo) * 2 + (m & 1);
-        v += bias[m];
+        if (bias) v += bias[m];
         if (res) v += res[o];
         y[o] = v;
     }
@@ -287,6 +289,42 @@ __global__ __launch_bounds__(256) void modrelu_bwd_kernel(const float2* __restri
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
+// The backward above as a function: dz = g + (b / r) P g, db = sum u . g where r + b > 0 (u = z / r, P = I - u u^T on (re, im) pairs).  With
+// S = <v, dz> + beta db:  dS/dg = v + (b / r) P v + beta u,  dS/db = sum <v, P g> / r,
+// dS/dz = -(b / r^2) (<v, P g> u + (u . g) P v + (u . v) P g) + (beta / r) P g.  At r = 0 the backward is dz = 0, db += g_re: dS/dg = (beta, 0).
+// v may be null (dz was not asked for: its cotangent is zero).
+__global__ __launch_bounds__(256) void modrelu_bwd2_kernel(const float2* __restrict__ g, const float2* __restrict__ z, const float* __restrict__ bp,
+                                                           const float2* __restrict__ v, const float* __restrict__ betap, float2* __restrict__ dg,
+                                                           float2* __restrict__ dz, float* __restrict__ part, long long n, long long span) {
+    const long long lo = (long long)blockIdx.x * span, hi = min(n, lo + span);
+    const float b = bp[0], beta = betap[0];
+    float s = 0.f;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+        const float2 zv = z[i], gv = g[i];
+        const float2 vv = v ? v[i] : make_float2(0.f, 0.f);
+        const float r = hypotf(zv.x, zv.y);
+        float2 og = {0.f, 0.f}, oz = {0.f, 0.f};
+        if (r + b > 0.f) {
+            if (r > 0.f) {
+                const float ux = zv.x / r, uy = zv.y / r, ug = ux * gv.x + uy * gv.y, uv = ux * vv.x + uy * vv.y, q = b / r;
+                const float pgx = gv.x - ux * ug, pgy = gv.y - uy * ug, pvx = vv.x - ux * uv, pvy = vv.y - uy * uv;
+                const float vpg = vv.x * pgx + vv.y * pgy, br = beta / r, q2 = q / r;
+                og.x = vv.x + q * pvx + beta * ux;
+                og.y = vv.y + q * pvy + beta * uy;
+                oz.x = br * pgx - q2 * (vpg * ux + ug * pvx + uv * pgx);
+                oz.y = br * pgy - q2 * (vpg * uy + ug * pvy + uv * pgy);
+                s += vpg / r;
+            } else {
+                og.x = beta;
+            }
+        }
+        dg[i] = og;
+        if (dz) dz[i] = oz;
+    }
+    s = block_sum(s);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
 __global__ __launch_bounds__(256) void sum_parts_kernel(const float* __restrict__ part, float* __restrict__ out, int nparts) {
     float s = 0.f;
     for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
@@ -307,6 +345,24 @@ __global__ __launch_bounds__(256) void cabs_bwd_kernel(const float* __restrict__
     float2 o = {0.f, 0.f};
     if (r > 0.f) o.x = g[i] * (v.x / r), o.y = g[i] * (v.y / r);
     dz[i] = o;
+}
+
+// dz = g u as a function of (g, z), against the cotangent v of dz: dS/dg = u . v, dS/dz = g P v / r; both 0 at r = 0
+__global__ __launch_bounds__(256) void cabs_bwd2_kernel(const float* __restrict__ g, const float2* __restrict__ z, const float2* __restrict__ v,
+                                                        float* __restrict__ dg, float2* __restrict__ dz, long long n) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float2 zv = z[i], vv = v[i];
+    const float r = hypotf(zv.x, zv.y);
+    float og = 0.f;
+    float2 oz = {0.f, 0.f};
+    if (r > 0.f) {
+        const float ux = zv.x / r, uy = zv.y / r, uv = ux * vv.x + uy * vv.y, q = g[i] / r;
+        og = uv;
+        oz.x = q * (vv.x - ux * uv), oz.y = q * (vv.y - uy * uv);
+    }
+    dg[i] = og;
+    if (dz) dz[i] = oz;
 }
 
 bool stft_ok(int B, int n, int n_fft, int hop, int F) { return B > 0 && n > 0 && n_fft > 0 && hop > 0 && F > 0 && F <= n_fft; }
@@ -424,6 +480,21 @@ extern "C" int alm_modrelu_bwd(const float* g, const float* z, const float* b, f
     return 0;
 }
 
+extern "C" int alm_modrelu_bwd2(const float* g, const float* z, const float* b, const float* v, const float* beta, float* dg, float* dz, float* db,
+                                float* ws, long long n, void* stream) {
+    if (g == nullptr || z == nullptr || b == nullptr || beta == nullptr || dg == nullptr || db == nullptr || ws == nullptr || n <= 0) return ALM_ERR_BAD_ARG;
+    long long span = RED_SPAN;
+    while ((n + span - 1) / span > RED_MAX_BLOCKS) span *= 2;
+    const int nparts = (int)((n + span - 1) / span);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(modrelu_bwd2_kernel, dim3(nparts), dim3(256), 0, st, (const float2*)g, (const float2*)z, b, (const float2*)v, beta, (float2*)dg,
+                       (float2*)dz, ws, n, span);
+    ALM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(256), 0, st, ws, db, nparts);
+    ALM_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int alm_cabs_fwd(const float* z, float* y, long long n, void* stream) {
     if (n <= 0) return ALM_ERR_BAD_ARG;
     if ((n + 255) / 256 >= I31) return ALM_ERR_UNSUPPORTED;
@@ -436,6 +507,15 @@ extern "C" int alm_cabs_bwd(const float* g, const float* z, float* dz, long long
     if (n <= 0) return ALM_ERR_BAD_ARG;
     if ((n + 255) / 256 >= I31) return ALM_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(cabs_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, (const float2*)z, (float2*)dz, n);
+    ALM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int alm_cabs_bwd2(const float* g, const float* z, const float* v, float* dg, float* dz, long long n, void* stream) {
+    if (g == nullptr || z == nullptr || v == nullptr || dg == nullptr || n <= 0) return ALM_ERR_BAD_ARG;
+    if ((n + 255) / 256 >= I31) return ALM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(cabs_bwd2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, (const float2*)z, (const float2*)v, dg,
+                       (float2*)dz, n);
     ALM_LAUNCH_CHECK();
     return 0;
 }

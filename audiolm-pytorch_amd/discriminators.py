@@ -10,11 +10,19 @@ LeakyReLU follows, its output (the activation's derivative is taken from the out
 `ComplexSTFTDiscriminator` (soundstream.py:173-310) follows the same rules on the kernels of csrc/stft_discr.hip: the STFT and every complex conv2d
 are implicit GEMMs on the exact-fp32 matrix core, the parameters keep the reference's names and real-view storage (`init_conv.*`,
 `layers.{i}.0.fn.{0,2}.*`, `layers.{i}.0.fn.1.b`, `layers.{i}.1.*`, `final_conv.*`), and `l1_loss` takes its complex64 intermediates.
+
+Double backward (the gradient penalty, soundstream.py:70-83).  Every `backward` below issues its launches through an autograd Function of its own
+(`_*BwdFn`, `_*DgradFn`), so that `torch.autograd.grad(..., create_graph=True)` records the input-gradient chain: a convolution is linear, so the
+derivative of its input-gradient kernel with respect to the incoming gradient is its forward kernel and the one with respect to the weight is its
+weight-gradient kernel, and the STFT likewise; ModReLU and |z| have second-order kernels.  Under a plain `backward()` torch runs these Functions without
+recording: the same launches with the same arguments.  What is not twice differentiable (weight gradients, the pooling backward, the MSE / L1 backward)
+raises `NotImplementedError` by name when something differentiates through it.  Nothing is differentiable a third time.
 """
 from __future__ import annotations
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import ops
 
@@ -31,6 +39,52 @@ def _f32c(t):
     if t.dtype != F32:
         raise TypeError(f'the discriminator kernels are fp32; got {t.dtype}')
     return t.contiguous()
+
+
+_WAVE_GRAD_ONLY = [False]     # set by gradient_penalty around its first pass: only the wave's gradient is asked for there (needs_input_grad is fixed
+                               # at forward time, so without it every weight gradient would be computed, recorded and thrown away)
+
+
+def _params_wanted(*flags):
+    return any(flags) and not _WAVE_GRAD_ONLY[0]
+
+
+def _no_double_backward(what):
+    raise NotImplementedError(f'double backward through {what} is not implemented (twice differentiable: the input gradients of the discriminator '
+                              'convolutions, of the STFT, of ModReLU and of |z|, which is what the gradient penalty needs)')
+
+
+class _GConvDgradFn(torch.autograd.Function):
+    """dx = gconv1d_dgrad(g, y, w); d/dg = m(y) conv(v, w), d/dw = gconv1d_wgrad(g, y, v), d/dy = 0 almost everywhere"""
+
+    @staticmethod
+    def forward(ctx, g, y, weight, Cin, Tin, stride, padding, groups):
+        ctx.cfg = (stride, padding, groups)
+        ctx.save_for_backward(g, y, weight)
+        return ops.gconv1d_dgrad(g, y, weight, Cin, Tin, stride=stride, padding=padding, groups=groups)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        g, y, weight = ctx.saved_tensors
+        stride, padding, groups = ctx.cfg
+        v = v.to(F32).contiguous()
+        dg = dw = None
+        if ctx.needs_input_grad[0]:
+            dg = ops.gconv1d_fwd_masked(v, weight, y, stride=stride, padding=padding, groups=groups)
+        if ctx.needs_input_grad[2]:
+            dw = ops.gconv1d_wgrad(g, y, v, weight.shape[2], stride=stride, padding=padding, groups=groups)[0]
+        return dg, None, dw, None, None, None, None, None
+
+
+class _GConvWgradFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, y, x, ksize, stride, padding, groups):
+        return ops.gconv1d_wgrad(g, y, x, ksize, stride=stride, padding=padding, groups=groups)
+
+    @staticmethod
+    def backward(ctx, *_):
+        _no_double_backward('the weight / bias gradient of a discriminator conv1d (gconv1d_wgrad)')
 
 
 class _GConv1dFn(torch.autograd.Function):
@@ -50,9 +104,9 @@ class _GConv1dFn(torch.autograd.Function):
         g = g.to(F32).contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = ops.gconv1d_dgrad(g, y, weight.detach(), x.shape[1], x.shape[2], stride=stride, padding=padding, groups=groups)
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = ops.gconv1d_wgrad(g, y, x, weight.shape[2], stride=stride, padding=padding, groups=groups)
+            dx = _GConvDgradFn.apply(g, y, weight, x.shape[1], x.shape[2], stride, padding, groups)
+        if _params_wanted(ctx.needs_input_grad[1], ctx.needs_input_grad[2]):
+            dw, db = _GConvWgradFn.apply(g, y, x, weight.shape[2], stride, padding, groups)
         return dx, dw, db, None, None, None, None
 
 
@@ -67,6 +121,16 @@ def conv1d_act(conv: nn.Conv1d, x, leaky=False):
     return ops.gconv1d(x.detach(), w.detach(), b.detach(), stride=stride, padding=padding, groups=groups, leaky=leaky)
 
 
+class _AvgPoolBwdFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, T, f):
+        return ops.avgpool1d_bwd(g, T, f)
+
+    @staticmethod
+    def backward(ctx, *_):
+        _no_double_backward('the pooling backward (avgpool1d_bwd)')
+
+
 class _AvgPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, f):
@@ -76,7 +140,7 @@ class _AvgPoolFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         T, f = ctx.cfg
-        return ops.avgpool1d_bwd(g.to(F32).contiguous(), T, f), None
+        return _AvgPoolBwdFn.apply(g.to(F32).contiguous(), T, f), None
 
 
 class AvgPoolDownsample(nn.AvgPool1d):
@@ -91,6 +155,22 @@ class AvgPoolDownsample(nn.AvgPool1d):
         return _AvgPoolFn.apply(x, self.factor) if _needs_graph(x) else ops.avgpool1d(x, self.factor)
 
 
+_LOSS_NAMES = {ops.LOSS_L1: 'the L1 loss', ops.LOSS_MSE: 'the squared-error loss', ops.LOSS_L1_COMPLEX: 'the complex L1 loss'}
+
+
+class _LossBwdFn(torch.autograd.Function):
+    """the backward of a loss mean whose derivative depends on its operands (L1, squared error, complex L1): not twice differentiable, by name"""
+
+    @staticmethod
+    def forward(ctx, a, b, g, mode, need_a, need_b):
+        ctx.mode = mode
+        return ops.loss_mean_bwd(mode, a, b, g, need_a, need_b)
+
+    @staticmethod
+    def backward(ctx, *_):
+        _no_double_backward(f'the backward of {_LOSS_NAMES[ctx.mode]} (loss_mean_bwd)')
+
+
 class _LossMeanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, mode):
@@ -102,7 +182,12 @@ class _LossMeanFn(torch.autograd.Function):
     def backward(ctx, g):
         a, b = ctx.saved_tensors
         need_b = b is not None and ctx.needs_input_grad[1]
-        da, db = ops.loss_mean_bwd(ctx.mode, a, b, g.to(F32).contiguous(), ctx.needs_input_grad[0], need_b)
+        g = g.to(F32).contiguous()
+        if ctx.mode in (ops.LOSS_HINGE_DISCR, ops.LOSS_HINGE_GEN):
+            # piecewise constant in the operands: the result is a constant of a second pass, which is its exact derivative almost everywhere
+            da, db = ops.loss_mean_bwd(ctx.mode, a.detach(), None if b is None else b.detach(), g.detach(), ctx.needs_input_grad[0], need_b)
+        else:
+            da, db = _LossBwdFn.apply(a, b, g, ctx.mode, ctx.needs_input_grad[0], need_b)
         return da, db, None
 
 
@@ -137,6 +222,46 @@ def mse_loss(a, b):
     return _loss(ops.LOSS_MSE, a, b)
 
 
+class _GradPenaltyFn(torch.autograd.Function):
+    """weight * mean_r (|G_r| - center)^2 of G [R, n] (csrc/discr.hip); its backward is a plain kernel"""
+
+    @staticmethod
+    def forward(ctx, G, weight, center):
+        out, norms = ops.grad_penalty(G, weight, center)
+        ctx.cfg = (weight, center)
+        ctx.save_for_backward(G, norms)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        G, norms = ctx.saved_tensors
+        return ops.grad_penalty_bwd(G, norms, gout.to(F32).contiguous(), *ctx.cfg), None, None
+
+
+def penalty_of_gradients(gradients, weight=10, center=0.):
+    """weight * mean_b (|G_b|_2 - center)^2 of the gradients (b, ...), the norm per batch row over everything else: the reduction of
+    `gradient_penalty`, differentiable once with respect to the gradients"""
+    G = _f32c(gradients).reshape(gradients.shape[0], -1)
+    return _GradPenaltyFn.apply(G, float(weight), float(center)) if _needs_graph(G) else ops.grad_penalty(G, float(weight), float(center))[0]
+
+
+def wave_gradients(wave, output):
+    """d output / d wave with `create_graph=True` (grad_outputs: ones), the first pass of `gradient_penalty`.  Only the wave's gradient is taken:
+    the native backward passes skip their parameter gradients meanwhile."""
+    _WAVE_GRAD_ONLY[0] = True
+    try:
+        return torch.autograd.grad(outputs=output, inputs=wave, grad_outputs=torch.ones_like(output), create_graph=True, retain_graph=True,
+                                   only_inputs=True)[0]
+    finally:
+        _WAVE_GRAD_ONLY[0] = False
+
+
+def gradient_penalty(wave, output, weight=10, center=0.):       # soundstream.py:70-83
+    """weight * mean_b (|d output / d wave_b|_2 - center)^2; the result backpropagates into whatever `output` depends on (double backward)"""
+    return penalty_of_gradients(wave_gradients(wave, output), weight, center)
+
+
 class MultiScaleDiscriminator(nn.Module):                        # soundstream.py:92-140
     def __init__(self, channels=16, layers=4, groups=(4, 16, 64, 256), chan_max=1024, input_channels=1):
         super().__init__()
@@ -165,6 +290,22 @@ class MultiScaleDiscriminator(nn.Module):                        # soundstream.p
 # ---- ComplexSTFTDiscriminator (soundstream.py:173-310) on the kernels of csrc/stft_discr.hip.  Inside the module a complex activation travels as its
 # fp32 [..., 2] (re, im) view; the intermediates handed out are torch.complex64 views of the same storage (view_as_complex: no copy, no kernel).
 
+class _StftBwdFn(torch.autograd.Function):
+    """dx = stft_bwd(g); d/dg = stft(v)"""
+
+    @staticmethod
+    def forward(ctx, g, basis, n, n_fft, hop):
+        ctx.cfg = (n_fft, hop)
+        ctx.basis = basis
+        return ops.stft_bwd(g, basis, n, n_fft, hop)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        n_fft, hop = ctx.cfg
+        return ops.stft(v.to(F32).contiguous(), ctx.basis, n_fft, hop), None, None, None, None
+
+
 class _StftFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, basis, n_fft, hop):
@@ -175,7 +316,40 @@ class _StftFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         n, n_fft, hop = ctx.cfg
-        return ops.stft_bwd(g.to(F32).contiguous(), ctx.basis, n, n_fft, hop), None, None, None
+        return _StftBwdFn.apply(g.to(F32).contiguous(), ctx.basis, n, n_fft, hop), None, None, None
+
+
+class _CConvDgradFn(torch.autograd.Function):
+    """dx = cconv2d_dgrad(g, w); d/dg = cconv2d(v, w) without bias or residual, d/dw = cconv2d_wgrad(g, v)"""
+
+    @staticmethod
+    def forward(ctx, g, weight, H, W, stride, padding):
+        ctx.cfg = (stride, padding)
+        ctx.save_for_backward(g, weight)
+        return ops.cconv2d_dgrad(g, weight, H, W, stride=stride, padding=padding)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        g, weight = ctx.saved_tensors
+        stride, padding = ctx.cfg
+        v = v.to(F32).contiguous()
+        dg = dw = None
+        if ctx.needs_input_grad[0]:
+            dg = ops.cconv2d(v, weight, None, stride=stride, padding=padding)
+        if ctx.needs_input_grad[1]:
+            dw = ops.cconv2d_wgrad(g, v, weight.shape[2:4], stride=stride, padding=padding)[0]
+        return dg, dw, None, None, None, None
+
+
+class _CConvWgradFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, x, kernel_size, stride, padding):
+        return ops.cconv2d_wgrad(g, x, kernel_size, stride=stride, padding=padding)
+
+    @staticmethod
+    def backward(ctx, *_):
+        _no_double_backward('the weight / bias gradient of a complex conv2d (cconv2d_wgrad)')
 
 
 class _CConv2dFn(torch.autograd.Function):
@@ -194,10 +368,29 @@ class _CConv2dFn(torch.autograd.Function):
         g = g.to(F32).contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = ops.cconv2d_dgrad(g, weight.detach(), x.shape[2], x.shape[3], stride=stride, padding=padding)
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = ops.cconv2d_wgrad(g, x, weight.shape[2:4], stride=stride, padding=padding)
+            dx = _CConvDgradFn.apply(g, weight, x.shape[2], x.shape[3], stride, padding)
+        if _params_wanted(ctx.needs_input_grad[1], ctx.needs_input_grad[2]):
+            dw, db = _CConvWgradFn.apply(g, x, tuple(weight.shape[2:4]), stride, padding)
         return dx, dw, db, (g if ctx.needs_input_grad[3] else None), None, None
+
+
+class _ModReLUBwdFn(torch.autograd.Function):
+    """(dz, db) = modrelu_bwd(g, z, b); its derivatives against the cotangents (v, beta) in one launch (csrc/stft_discr.hip modrelu_bwd2_kernel)"""
+
+    @staticmethod
+    def forward(ctx, g, z, b, need_dz):
+        ctx.save_for_backward(g, z, b)
+        ctx.need_dz = need_dz
+        dz, db = ops.modrelu_bwd(g, z, b, need_dz=need_dz)
+        return dz, db
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v, beta):
+        g, z, b = ctx.saved_tensors
+        v = v.to(F32).contiguous() if ctx.need_dz else None
+        dg, dz, db = ops.modrelu_bwd2(g, z, b, v, beta.to(F32).contiguous(), need_dz=ctx.needs_input_grad[1])
+        return dg, dz, (db if ctx.needs_input_grad[2] else None), None
 
 
 class _ModReLUFn(torch.autograd.Function):
@@ -209,8 +402,24 @@ class _ModReLUFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         z, b = ctx.saved_tensors
-        dz, db = ops.modrelu_bwd(g.to(F32).contiguous(), z, b.detach(), need_dz=ctx.needs_input_grad[0])
+        dz, db = _ModReLUBwdFn.apply(g.to(F32).contiguous(), z, b, ctx.needs_input_grad[0])
         return dz, (db if ctx.needs_input_grad[1] else None)
+
+
+class _CAbsBwdFn(torch.autograd.Function):
+    """dz = complex_abs_bwd(g, z) = g u; d/dg = u . v, d/dz = g P v / |z|"""
+
+    @staticmethod
+    def forward(ctx, g, z):
+        ctx.save_for_backward(g, z)
+        return ops.complex_abs_bwd(g, z)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        g, z = ctx.saved_tensors
+        dg, dz = ops.complex_abs_bwd2(g, z, v.to(F32).contiguous(), need_dz=ctx.needs_input_grad[1])
+        return dg, dz
 
 
 class _CAbsFn(torch.autograd.Function):
@@ -222,7 +431,7 @@ class _CAbsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         z, = ctx.saved_tensors
-        return ops.complex_abs_bwd(g.to(F32).contiguous(), z)
+        return _CAbsBwdFn.apply(g.to(F32).contiguous(), z)
 
 
 def _as_pairs(x):

@@ -1584,6 +1584,18 @@ def gconv1d(x, w, bias, *, stride=1, padding=0, groups=1, leaky=False):
     return y
 
 
+def gconv1d_fwd_masked(v, w, y, *, stride=1, padding=0, groups=1):
+    """v fp32 [B, Cin, Tin] -> m(y) conv1d(v, w) fp32 [B, Cout, Tout] without a bias, m(y) = 1 where the saved output y > 0 and 0.1 elsewhere (y None:
+    no mask): the derivative of gconv1d_dgrad(g, y, w) with respect to g, applied to v"""
+    assert all(_chk(t, F32).is_contiguous() for t in (v, w))
+    B, Cin, Cout, Tin, K, Tout = _gconv_dims(v, w, stride, padding, groups)
+    if y is not None:
+        assert _chk(y, F32).shape == (B, Cout, Tout) and y.is_contiguous()
+    out = _new((B, Cout, Tout), dtype=F32, device=v.device)
+    _lib.call('alm_gconv1d_fwd_masked', v.data_ptr(), w.data_ptr(), _p(y), out.data_ptr(), B, Cin, Cout, Tin, K, stride, padding, groups, _st())
+    return out
+
+
 def gconv1d_dgrad(g, y, w, Cin, Tin, *, stride=1, padding=0, groups=1):
     """g fp32 [B, Cout, Tout] = dL/dout (times LeakyReLU'(.) taken from the saved output y when y is given) -> dL/dx fp32 [B, Cin, Tin] of gconv1d"""
     assert all(_chk(t, F32).is_contiguous() for t in (g, w))
@@ -1658,6 +1670,29 @@ def loss_mean_bwd(mode, a, b, gout, need_a=True, need_b=True):
     db = _new_like(b) if need_b and b is not None else None
     _lib.call('alm_loss_mean_bwd', a.data_ptr(), _p(b), gout.data_ptr(), _p(da), _p(db), a.numel() // (2 if mode == LOSS_L1_COMPLEX else 1), mode, _st())
     return da, db
+
+
+def grad_penalty(G, weight=10., center=0.):
+    """G fp32 [R, n] -> (weight / R sum_r (|G_r| - center)^2 as a 0-dim fp32, the R row norms), every sum in a fixed order"""
+    assert _chk(G, F32).is_contiguous() and G.ndim == 2
+    R, n = G.shape
+    nws = _lib.query('alm_grad_penalty_ws_floats', R, n)
+    if nws < 0:
+        raise _lib.AlmError(f'grad_penalty: {R} x {n} is outside the kernel envelope (1 .. 65535 non-empty rows)')
+    out = _new((), dtype=F32, device=G.device)
+    norms = _new((R,), dtype=F32, device=G.device)
+    ws = _new((nws,), dtype=F32, device=G.device)
+    _lib.call('alm_grad_penalty_fwd', G.data_ptr(), out.data_ptr(), norms.data_ptr(), ws.data_ptr(), nws, R, n, float(weight), float(center), _st())
+    return out, norms
+
+
+def grad_penalty_bwd(G, norms, gout, weight=10., center=0.):
+    """d grad_penalty / dG given the upstream gradient gout (0-dim fp32, read on the device); 0 for a row of norm 0"""
+    assert all(_chk(t, F32).is_contiguous() for t in (G, norms)) and G.ndim == 2 and norms.shape == (G.shape[0],) and _chk(gout, F32).numel() == 1
+    dG = _new_like(G)
+    _lib.call('alm_grad_penalty_bwd', G.data_ptr(), norms.data_ptr(), gout.data_ptr(), dG.data_ptr(), G.shape[0], G.shape[1], float(weight), float(center),
+              _st())
+    return dG
 
 
 # ---- ComplexSTFTDiscriminator of SoundStream training (csrc/stft_discr.hip), fp32, no atomics.  Complex tensors travel as fp32 [..., 2] (re, im) pairs.
@@ -1747,14 +1782,14 @@ def _cconv_dims(xshape, wshape, stride, padding):
 
 def cconv2d(x, w, bias, *, stride=1, padding=0, residual=None):
     """x fp32 [B, Cin, H, W, 2], w fp32 [Cout, Cin, kh, kw, 2], bias fp32 [Cout, 2] (view_as_real of a complex nn.Conv2d's parameters)
-    -> view_as_real(F.conv2d(x, w, bias, stride, padding)) fp32 [B, Cout, Ho, Wo, 2] (+ residual of that shape)"""
-    assert all(_chk(t, F32).is_contiguous() for t in (x, w, bias))
+    -> view_as_real(F.conv2d(x, w, bias, stride, padding)) fp32 [B, Cout, Ho, Wo, 2] (+ residual of that shape); bias None: no bias"""
+    assert all(_chk(t, F32).is_contiguous() for t in (x, w))
     dims, (Ho, Wo) = _cconv_dims(x.shape, w.shape, stride, padding)
-    assert bias.shape == (dims[2], 2)
+    assert bias is None or (_chk(bias, F32).is_contiguous() and bias.shape == (dims[2], 2))
     y = _new((dims[0], dims[2], Ho, Wo, 2), dtype=F32, device=x.device)
     if residual is not None:
         assert _chk(residual, F32).is_contiguous() and residual.shape == y.shape
-    _lib.call('alm_cconv2d_fwd', x.data_ptr(), w.data_ptr(), bias.data_ptr(), _p(residual), y.data_ptr(), *dims, _st())
+    _lib.call('alm_cconv2d_fwd', x.data_ptr(), w.data_ptr(), _p(bias), _p(residual), y.data_ptr(), *dims, _st())
     return y
 
 
@@ -1801,6 +1836,31 @@ def modrelu_bwd(g, z, b, need_dz=True):
     ws = _new((_lib.query('alm_modrelu_ws_floats'),), dtype=F32, device=z.device)
     _lib.call('alm_modrelu_bwd', g.data_ptr(), z.data_ptr(), b.data_ptr(), _p(dz), db.data_ptr(), ws.data_ptr(), z.numel() // 2, _st())
     return dz, db
+
+
+def modrelu_bwd2(g, z, b, v, beta, need_dz=True):
+    """modrelu_bwd as a function of (g, z, b) against the cotangents v (of dz; None: zero) and beta (0-dim, of db; read on the device), one launch:
+    (d/dg, d/dz | None, d/db 0-dim); d/db is summed in the two fixed-order stages of modrelu_bwd"""
+    assert all(_chk(t, F32).is_contiguous() for t in (g, z)) and g.shape == z.shape and z.shape[-1] == 2
+    assert _chk(b, F32).numel() == 1 and _chk(beta, F32).numel() == 1
+    if v is not None:
+        assert _chk(v, F32).is_contiguous() and v.shape == z.shape
+    dg = _new_like(z)
+    dz = _new_like(z) if need_dz else None
+    db = _new((), dtype=F32, device=z.device)
+    ws = _new((_lib.query('alm_modrelu_ws_floats'),), dtype=F32, device=z.device)
+    _lib.call('alm_modrelu_bwd2', g.data_ptr(), z.data_ptr(), b.data_ptr(), _p(v), beta.data_ptr(), dg.data_ptr(), _p(dz), db.data_ptr(), ws.data_ptr(),
+              z.numel() // 2, _st())
+    return dg, dz, db
+
+
+def complex_abs_bwd2(g, z, v, need_dz=True):
+    """complex_abs_bwd as a function of (g, z) against the cotangent v of dz: (d/dg = u . v, d/dz = g P v / |z| | None); 0 at z = 0"""
+    assert all(_chk(t, F32).is_contiguous() for t in (g, z, v)) and tuple(z.shape) == (*g.shape, 2) and v.shape == z.shape
+    dg = _new_like(g)
+    dz = _new_like(z) if need_dz else None
+    _lib.call('alm_cabs_bwd2', g.data_ptr(), z.data_ptr(), v.data_ptr(), dg.data_ptr(), _p(dz), g.numel(), _st())
+    return dg, dz
 
 
 def complex_abs(z):

@@ -5,7 +5,8 @@ return_codes_only=True)` -- the causal-conv encoder (soundstream.py:332-380, 519
 decoder :347-360, 382-395, 615-627) run on the MI355X kernels of csrc/codec.hip (exact-fp32 MFMA).  The training losses (soundstream.py:868-995:
 three wave MultiScaleDiscriminators, hinge / feature / reconstruction terms) are opt-in, `with_discriminators=True` (discriminators.py,
 csrc/discr.hip), and so are the ComplexSTFTDiscriminator, `stft_discriminator=True` (csrc/stft_discr.hip), and the multi-spectral mel-spectrogram
-reconstruction loss, `with_mel_loss=True` (mel_loss.py, csrc/mel_loss.hip); the gradient penalty and the LFQ / FSQ quantizers are out of scope and raise.  In training mode the quantizer takes one
+reconstruction loss, `with_mel_loss=True` (mel_loss.py, csrc/mel_loss.hip), and the gradient penalty of the discriminator loss, `with_grad_penalty=True`
+(a double backward through the discriminator kernels); the LFQ / FSQ quantizers are out of scope and raise.  In training mode the quantizer takes one
 training step per call (csrc/rvq_train.hip: quantize dropout, commitment loss, rotation trick, EMA codebooks with dead-code expiry, k-means
 initialisation; single process only), so `forward(x, return_recons_only=True | return_encoded=True)` is differentiable end to end.  The conv encoder / decoder are
 differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
@@ -537,7 +538,10 @@ def curtail_to_multiple(t, mult, from_left=False):               # soundstream.p
 
 
 class SoundStream(nn.Module):
-    """Constructor keywords and defaults follow the reference (soundstream.py:451-510); options outside the tokenize path raise."""
+    """Constructor keywords and defaults follow the reference (soundstream.py:451-510); options outside the tokenize path raise.  The training losses
+    are opt-in switches of this port: `with_discriminators=True` (wave discriminators and loss branches), on top of it `stft_discriminator=True`,
+    `with_mel_loss=True` and `with_grad_penalty=True` (lets `forward(..., return_discr_loss=True, apply_grad_penalty=True)` add the reference's
+    gradient penalties; registers no parameter, buffer or child module, so the state_dict is the same with and without it)."""
 
     def __init__(self, *, channels=32, strides=(2, 4, 5, 8), channel_mults=(2, 4, 8, 16), codebook_dim=512, codebook_size=None,
                  finite_scalar_quantizer_levels=None, rq_num_quantizers=8, rq_commitment_weight=1., rq_ema_decay=0.95,
@@ -548,7 +552,7 @@ class SoundStream(nn.Module):
                  attn_xpos_scale_base=None, attn_dynamic_pos_bias=False, use_gate_loop_layers=False, squeeze_excite=False, pad_mode='reflect',
                  stft_discriminator=None, with_discriminators=False, stft_normalized=False, complex_stft_discr_logits_abs=True,
                  complex_stft_discr_kwargs: dict = {}, with_mel_loss=False, multi_spectral_window_powers_of_two=tuple(range(6, 12)),
-                 multi_spectral_n_ffts=512, multi_spectral_n_mels=64, **kwargs):
+                 multi_spectral_n_ffts=512, multi_spectral_n_mels=64, with_grad_penalty=False, **kwargs):
         super().__init__()
         if use_lookup_free_quantizer or use_finite_scalar_quantizer or finite_scalar_quantizer_levels is not None:
             raise NotImplementedError('LFQ / FSQ quantizers are out of scope (SURVEY.md §2)')
@@ -618,6 +622,11 @@ class SoundStream(nn.Module):
                 self.mel_spec_transforms.append(mel_loss.MelSpectrogram(sample_rate=target_sample_hz, n_fft=max(n_fft, win_length), win_length=win_length,
                                                                         hop_length=win_length // 4, n_mels=mels, normalized=stft_normalized))
                 self.mel_spec_recon_alphas.append((win_length / 2) ** 0.5)
+        # the gradient penalty (soundstream.py:883-898) is opt-in on top: a switch only, no parameter, buffer or child module; without it
+        # `apply_grad_penalty=True` raises, like before
+        self.with_grad_penalty = bool(with_grad_penalty)
+        if self.with_grad_penalty and not self.with_discriminators:
+            raise ValueError('with_grad_penalty=True needs with_discriminators=True (the penalty is part of the discriminator loss)')
         self.eval()
 
     @property
@@ -675,7 +684,10 @@ class SoundStream(nn.Module):
         nothing is recorded for autograd and commit_loss is zero; in training mode the quantizer takes one training step (GroupedResidualVQ) and,
         with grad mode on, the results carry a graph through encoder, quantizer and decoder.  The loss branches (soundstream.py:868-995) need
         `with_discriminators=True` at construction and raise without it: return_discr_loss (with return_discr_losses_separately: the list of
-        ('scale:{s}', loss) / ('stft', loss) pairs) works on the input and the detached reconstruction; otherwise the generator's total loss, with
+        ('scale:{s}', loss) / ('stft', loss) pairs) works on the input and the detached reconstruction, with `apply_grad_penalty=True` (needs
+        `with_grad_penalty=True` at construction) plus the reference's gradient penalties: 'stft_grad_penalty' in the total and in the package,
+        'scale_grad_penalty:{s}' in the package only, labelled as the reference labels them; otherwise the generator's total loss (which ignores
+        apply_grad_penalty), with
         return_loss_breakdown also (recon, multi_spectral, adversarial, feature, commitment).  `target=` replaces the input in the recon term."""
         codec_only = return_encoded or return_codes_only or return_recons_only
         if not self.with_discriminators and (target is not None or is_denoising is not None or return_discr_loss or return_discr_losses_separately
@@ -703,7 +715,7 @@ class SoundStream(nn.Module):
                 return recon.reshape(*lead, recon.shape[-2], recon.shape[-1])
             orig_x = x.to(F32).contiguous()
             if return_discr_loss:
-                return self._discr_loss(orig_x, recon.detach(), return_discr_losses_separately)
+                return self._discr_loss(orig_x, recon.detach(), return_discr_losses_separately, apply_grad_penalty)
             if target is not None:
                 target, _ = self.process_input(target, input_sample_hz=input_sample_hz, curtail_from_left=curtail_from_left)
             return self._generator_loss(orig_x, recon, orig_x if target is None else target.to(F32).contiguous(), commit_loss, return_loss_breakdown)
@@ -713,9 +725,9 @@ class SoundStream(nn.Module):
         if self.multi_spectral_recon_loss_weight > 0 and not self.with_mel_loss:
             raise NotImplementedError('the multi-spectral mel-spectrogram reconstruction loss (torchaudio MelSpectrogram) is not constructed by default: '
                                       'pass with_mel_loss=True for the native one, or construct the SoundStream with multi_spectral_recon_loss_weight=0')
-        if apply_grad_penalty:
+        if apply_grad_penalty and not self.with_grad_penalty:
             raise NotImplementedError('apply_grad_penalty=True (gradient penalty) needs a double backward through the discriminator kernels, which is '
-                                      'not implemented')
+                                      'opt-in: construct the SoundStream with with_grad_penalty=True')
         if getattr(self, 'stft_discriminator', None) is None and not self._stft_discriminator_off:
             raise NotImplementedError('the ComplexSTFTDiscriminator is not constructed by default: pass stft_discriminator=True for the native one, '
                                       'stft_discriminator=<an nn.Module with forward(x, return_intermediates=False)>, or stft_discriminator=False '
@@ -724,14 +736,27 @@ class SoundStream(nn.Module):
     def _mel_term_on(self):
         return self.with_mel_loss and self.multi_spectral_recon_loss_weight > 0
 
-    def _scales(self, real, fake):
-        """per wave discriminator (logits, intermediates) of real and fake run as ONE batch [real | fake] through the chain of downsamples"""
+    def _scales(self, real, fake, leaves=None):
+        """per wave discriminator (logits, intermediates) of real and fake run as ONE batch [real | fake] through the chain of downsamples.  With a
+        list `leaves`, the wave handed to each discriminator is a fresh leaf that requires grad (appended to the list) for the gradient penalty; the
+        chain of downsamples runs on the plain waves, so the pooling stays out of the penalty's graph."""
         b = real.shape[0]
         scaled = torch.cat((real, fake), dim=0)
         for discr, downsample in zip(self.discriminators, self.downsamples):
             scaled = downsample(scaled)
-            logits, inter = discr(scaled, return_intermediates=True)
+            wave = scaled
+            if leaves is not None:
+                wave = scaled.detach().requires_grad_()
+                leaves.append(wave)
+            logits, inter = discr(wave, return_intermediates=True)
             yield (logits[:b], logits[b:]), [(t[:b], t[b:]) for t in inter]
+
+    @staticmethod
+    def _penalty_pair(wave, loss, b):
+        """(gradient_penalty(real, loss), gradient_penalty(fake, loss)) from ONE autograd.grad with respect to the batch [real | fake]: rows [:b] make
+        the real penalty and rows [b:] the fake one, each a mean over its own b rows"""
+        gradients = D.wave_gradients(wave, loss)
+        return D.penalty_of_gradients(gradients[:b]), D.penalty_of_gradients(gradients[b:])
 
     def _stft(self, real, fake, return_intermediates):
         """(real, fake) outputs of the STFT discriminator: the native module takes ONE batch [real | fake] like `_scales` (every op is
@@ -748,18 +773,45 @@ class SoundStream(nn.Module):
         logits, inter = out
         return (logits[:b], [t[:b] for t in inter]), (logits[b:], [t[b:] for t in inter])
 
-    def _discr_loss(self, real, fake, separately):               # soundstream.py:870-925 (without the gradient penalties)
-        stft_loss = None
+    def _discr_loss(self, real, fake, separately, penalty=False):               # soundstream.py:870-925
+        b = real.shape[0]
+        stft_loss = stft_penalty = None
         if not self._stft_discriminator_off and self.single_channel:
-            stft_real_logits, stft_fake_logits = self._stft(real, fake, False)
-            stft_loss = D.hinge_discr_loss(stft_fake_logits, stft_real_logits)
-        losses = [D.hinge_discr_loss(fake_logits, real_logits) for (real_logits, fake_logits), _ in self._scales(real, fake)]
+            discr = self.stft_discriminator
+            if not penalty:
+                stft_real_logits, stft_fake_logits = self._stft(real, fake, False)
+                stft_loss = D.hinge_discr_loss(stft_fake_logits, stft_real_logits)
+            elif isinstance(discr, D.ComplexSTFTDiscriminator):
+                wave = torch.cat((real, fake), dim=0).detach().requires_grad_()
+                logits = discr(wave)
+                stft_loss = D.hinge_discr_loss(logits[b:], logits[:b])
+                penalty_real, penalty_fake = self._penalty_pair(wave, stft_loss, b)
+                stft_penalty = penalty_real + penalty_fake
+            else:                                                # a caller's own module: its two separate calls, torch's autograd through it
+                real_leaf, fake_leaf = real.detach().clone().requires_grad_(), fake.detach().clone().requires_grad_()
+                stft_loss = D.hinge_discr_loss(discr(fake_leaf), discr(real_leaf))
+                stft_penalty = D.gradient_penalty(real_leaf, stft_loss) + D.gradient_penalty(fake_leaf, stft_loss)
+        # the wave discriminators' penalties reach the result only in the package (the reference computes them and drops them from the total)
+        leaves = [] if penalty and separately else None
+        losses, penalties = [], []
+        for (real_logits, fake_logits), _ in self._scales(real, fake, leaves):
+            losses.append(D.hinge_discr_loss(fake_logits, real_logits))
+            if leaves is not None:
+                penalties.extend(self._penalty_pair(leaves[-1], losses[-1], b))           # real, then fake
         if not separately:
             total = torch.stack(losses).mean()
-            return total if stft_loss is None else total + stft_loss
+            if stft_loss is not None:
+                total = total + stft_loss
+            return total if stft_penalty is None else total + stft_penalty
         pkg = [(f'scale:{scale}', loss) for scale, loss in zip(self.discr_multi_scales, losses)]
+        # The reference zips its scales with the FLAT list [real, fake] per scale (soundstream.py:917), so the labels pair the 3 scales with the first
+        # 3 of 6 penalties: with the default scales 'scale_grad_penalty:1' is real at scale 1, 'scale_grad_penalty:0.5' is FAKE at scale 1 and
+        # 'scale_grad_penalty:0.25' is REAL at scale 0.5.  Mirrored exactly: checkpoint and log comparisons against the reference depend on it.
+        pkg.extend((f'scale_grad_penalty:{scale}', p) for scale, p in zip(self.discr_multi_scales, penalties))
         if stft_loss is not None:
             pkg.append(('stft', stft_loss))
+        if stft_penalty is not None:
+            pkg.append(('stft_grad_penalty', stft_penalty))
         return pkg
 
     def _generator_loss(self, real, fake, target, commit_loss, breakdown):      # soundstream.py:927-995

@@ -592,6 +592,10 @@ int alm_gconv1d_fwd(const float* x, const float* w, const float* bias, float* y,
                     int groups, int act, void* stream);
 int alm_gconv1d_dgrad(const float* g, const float* y, const float* w, float* dx, int B, int Cin, int Cout, int Tin, int ksize, int stride, int padding,
                       int groups, void* stream);
+/* out [B][Cout][Tout] = m(y) conv1d(v, w) without a bias, m(y) = 1 where the saved output y > 0 and 0.1 elsewhere (y null: no mask): the derivative of
+ * alm_gconv1d_dgrad(g, y, w) with respect to g applied to v [B][Cin][Tin] (double backward of the gradient penalty); the tiling of alm_gconv1d_fwd. */
+int alm_gconv1d_fwd_masked(const float* v, const float* w, const float* y, float* out, int B, int Cin, int Cout, int Tin, int ksize, int stride,
+                           int padding, int groups, void* stream);
 int alm_gconv1d_wgrad_ws_floats(int B, int Cin, int Cout, int Tin, int ksize, int stride, int padding, int groups);
 int alm_gconv1d_wgrad(const float* g, const float* y, const float* x, float* dw, float* db, float* ws, long long ws_floats, int B, int Cin, int Cout,
                       int Tin, int ksize, int stride, int padding, int groups, void* stream);
@@ -601,6 +605,14 @@ int alm_avgpool1d_bwd(const float* g, float* dx, long long rows, int T, int f, v
 int alm_loss_ws_floats(void);
 int alm_loss_mean_fwd(const float* a, const float* b, float* out, float* ws, long long n, int mode, void* stream);
 int alm_loss_mean_bwd(const float* a, const float* b, const float* gout, float* da, float* db, long long n, int mode, void* stream);
+/* gradient penalty (soundstream.py:70-83) of G [R][n]: out[0] = weight / R sum_r (|G_r| - center)^2, norms [R] = |G_r| kept for the backward.  A row's
+ * squares are summed per block over contiguous spans in a fixed lane order, the partials in index order (ws: alm_grad_penalty_ws_floats(R, n) floats,
+ * -1 outside the envelope R <= 65535).  _bwd: dG = gout[0] weight 2 (|G_r| - center) / R G / |G_r| (0 for a row of norm 0); gout is read from device
+ * memory. */
+int alm_grad_penalty_ws_floats(int R, long long n);
+int alm_grad_penalty_fwd(const float* G, float* out, float* norms, float* ws, long long ws_floats, int R, long long n, float weight, float center,
+                         void* stream);
+int alm_grad_penalty_bwd(const float* G, const float* norms, const float* gout, float* dG, int R, long long n, float weight, float center, void* stream);
 
 /* ---- ComplexSTFTDiscriminator of SoundStream training (csrc/stft_discr.hip), fp32, no atomics -------------------------------------------------------
  * Complex tensors are interleaved (re, im) pairs (torch.complex64's storage); a gradient is the pair (dL/dre, dL/dim) (reference soundstream.py:173-310).
@@ -614,13 +626,19 @@ int alm_loss_mean_bwd(const float* a, const float* b, const float* gout, float* 
  * alm_cconv2d_* : zero-padded complex conv2d, dilation 1.  x [B][Cin][H][W][2], w [Cout][Cin][kh][kw][2] and bias [Cout][2] (view_as_real of a complex
  *     nn.Conv2d's parameters, read as they are), y [B][Cout][Ho][Wo][2] = conv + bias (+ residual [B][Cout][Ho][Wo][2] when not null).
  *     alm_cconv2d_out_hw writes Ho = (H + 2 ph - kh) / sh + 1 and Wo and returns 0, or -1 when the padded input is smaller than the kernel.
- *   alm_cconv2d_dgrad : dx [B][Cin][H][W][2] from g = dL/dy.
+ *   alm_cconv2d_dgrad : dx [B][Cin][H][W][2] from g = dL/dy.  Its derivative with respect to g is alm_cconv2d_fwd with a null bias (bias and
+ *                       residual of alm_cconv2d_fwd may be null: nothing is added).
  *   alm_cconv2d_wgrad : dw in the parameter's layout, db [Cout][2]; partial sums per split of the (b, ho, wo) list into ws
  *                       (alm_cconv2d_wgrad_ws_floats floats, caller-owned; -1: outside the kernel's envelope), then added in split order.
  * alm_modrelu_fwd : y = relu(|z| + b) z / |z| over n complex elements, b a scalar in device memory; z = 0 gives relu(b) + 0i.
  * alm_modrelu_bwd : where |z| + b > 0, with u = z / |z|: dz = g + b (g - u (u . g)) / |z| and db += u . g (at z = 0: dz = 0, db += g_re); else 0.
  *     dz may be null; db[0] is summed in two fixed-order stages through ws (alm_modrelu_ws_floats floats).
- * alm_cabs_fwd / _bwd : y = |z| [n] and dz = g z / |z| (0 at z = 0). */
+ * alm_cabs_fwd / _bwd : y = |z| [n] and dz = g z / |z| (0 at z = 0).
+ * Second order (double backward of the gradient penalty), with u = z / |z|, r = |z|, P = I - u u^T on (re, im) pairs:
+ * alm_modrelu_bwd2 : alm_modrelu_bwd as a function of (g, z, b) against the cotangents v [n][2] of dz (null: zero) and beta[0] (device) of db, one
+ *     launch: dg = v + (b / r) P v + beta u;  dz = -(b / r^2) (<v, P g> u + (u . g) P v + (u . v) P g) + (beta / r) P g (may be null);
+ *     db[0] = sum <v, P g> / r in the two fixed-order stages of alm_modrelu_bwd (same ws); all 0 where |z| + b <= 0; at z = 0: dg = (beta, 0).
+ * alm_cabs_bwd2 : alm_cabs_bwd against the cotangent v of dz: dg [n] = u . v, dz = g P v / r (may be null); both 0 at z = 0. */
 int alm_stft_frames(int n, int n_fft, int hop);
 int alm_stft_fwd(const float* x, const float* basis, float* X, int B, int n, int n_fft, int hop, int F, void* stream);
 int alm_stft_bwd_ws_floats(int B, int n, int n_fft, int hop);
@@ -638,6 +656,9 @@ int alm_modrelu_fwd(const float* z, const float* b, float* y, long long n, void*
 int alm_modrelu_bwd(const float* g, const float* z, const float* b, float* dz, float* db, float* ws, long long n, void* stream);
 int alm_cabs_fwd(const float* z, float* y, long long n, void* stream);
 int alm_cabs_bwd(const float* g, const float* z, float* dz, long long n, void* stream);
+int alm_modrelu_bwd2(const float* g, const float* z, const float* b, const float* v, const float* beta, float* dg, float* dz, float* db, float* ws,
+                     long long n, void* stream);
+int alm_cabs_bwd2(const float* g, const float* z, const float* v, float* dg, float* dz, long long n, void* stream);
 
 /* ---- multi-spectral mel-spectrogram reconstruction loss of SoundStream training (csrc/mel_loss.hip), fp32, no atomics ---------------------------------
  * torchaudio.transforms.MelSpectrogram (power 2, center, reflect, one-sided, HTK) per scale and the two per-frame norms of reference

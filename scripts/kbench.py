@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty]"""
 import os
 import sys
 import time
@@ -917,6 +917,85 @@ def bench_mel_loss():
             names = ('power', 'project', 'frame loss (2)', 'column grad', 'dP -> dX', 'stft bwd (2)')
             print(f'    win {t.win_length:4d} n_fft {t.n_fft:4d} hop {t.hop_length:3d} T {mel.shape[-1]:5d}: hand {t_o:.3f} ms   ATen {t_a:.3f} ms   hand / ATen '
                   f'{t_o / t_a:.2f}   launches: ' + ', '.join(f'{k} {v * 1e3:.0f} us' for k, v in zip(names, parts)), flush=True)
+
+
+def bench_grad_penalty():
+    """Discriminator step of SoundStream training with and without the gradient penalty at a training-like shape: B = 8, one second at 24 kHz, the
+    three default MultiScaleDiscriminators and the default ComplexSTFTDiscriminator.  One step = the discriminator branch with
+    return_discr_losses_separately=True on fixed real / fake waves (the codec is left out), then backward over every package entry with
+    retain_graph=True, as the reference's trainer does.  Beside it, as a yardstick, the wave discriminators' penalties alone (three scales, real and
+    fake, each entry's backward) on the native double backward and composed from torch's own conv1d + autograd (ATen, fp32) on the same box.
+    Interleaved rounds, medians, one event pair per call."""
+    import torch.nn.functional as F
+    from audiolm_pytorch_amd import discriminators as D
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def median(fns, rounds=10, warm=3):
+        for _ in range(warm):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(rounds):
+            for t, fn in zip(ts, fns):
+                t.append(once(fn))
+        return [sorted(t)[len(t) // 2] for t in ts]
+
+    B, n = 8, 24000
+    torch.manual_seed(0)
+    ss = A.SoundStream(channels=4, codebook_dim=16, codebook_size=32, rq_num_quantizers=4, use_local_attn=False, multi_spectral_recon_loss_weight=0.,
+                       stft_discriminator=True, with_discriminators=True, with_grad_penalty=True).to(dev).train()
+    real, fake = torch.randn(B, 1, n, device=dev) * 0.3, torch.randn(B, 1, n, device=dev) * 0.3
+
+    def step(penalty):
+        ss.zero_grad(set_to_none=True)
+        for _, loss in ss._discr_loss(real, fake, True, penalty):
+            loss.backward(retain_graph=True)
+
+    t_plain, t_pen = median([lambda: step(False), lambda: step(True)])
+    print(f'grad_penalty {B} x {n}: discriminator step, backward per package entry: without the penalty (4 entries) {t_plain:.2f} ms   with it (8 entries) '
+          f'{t_pen:.2f} ms   ratio {t_pen / t_plain:.2f}', flush=True)
+
+    def aten_discr(m, x):
+        x = m.init_conv(x)
+        for layer in m.conv_layers:
+            x = F.leaky_relu(layer[0](x), 0.1)
+        return m.final_conv[2](F.leaky_relu(m.final_conv[0](x), 0.1))
+
+    def aten_penalty(wave, loss):
+        g, = torch.autograd.grad(loss, wave, torch.ones_like(loss), create_graph=True)
+        return 10 * (torch.linalg.vector_norm(g.reshape(g.shape[0], -1), dim=1) ** 2).mean()
+
+    def wave_penalties(native):
+        ss.zero_grad(set_to_none=True)
+        scaled = torch.cat((real, fake))
+        for d, down in zip(ss.discriminators, ss.downsamples):
+            scaled = down(scaled)
+            if native:
+                wave = scaled.detach().requires_grad_()
+                logits = d(wave)
+                pens = ss._penalty_pair(wave, D.hinge_discr_loss(logits[B:], logits[:B]), B)
+            else:
+                r, f = scaled[:B].detach().requires_grad_(), scaled[B:].detach().requires_grad_()
+                loss = (F.relu(1 + aten_discr(d, f)) + F.relu(1 - aten_discr(d, r))).mean()
+                pens = aten_penalty(r, loss), aten_penalty(f, loss)
+            for p in pens:
+                p.backward(retain_graph=True)
+
+    try:
+        t_o, t_a = median([lambda: wave_penalties(True), lambda: wave_penalties(False)])
+        print(f'grad_penalty {B} x {n}: wave discriminators\' penalties alone (3 scales x real, fake; fwd + double backward per entry): hand {t_o:.2f} ms   '
+              f'ATen {t_a:.2f} ms   hand / ATen {t_o / t_a:.2f}', flush=True)
+    except Exception as e:                                       # the yardstick is optional: say so and keep the native numbers
+        t_o, = median([lambda: wave_penalties(True)])
+        print(f'grad_penalty {B} x {n}: wave discriminators\' penalties alone: hand {t_o:.2f} ms   ATen did not run ({type(e).__name__}: {e})', flush=True)
 
 
 if __name__ == '__main__':
