@@ -193,6 +193,13 @@ SIGNATURES = {
     'alm_mel_frame_loss_fwd': [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     'alm_mel_frame_loss_bwd': [_P, _P, _P, _P, _I, _I, _I, _F, _P],
     'alm_mel_power_bwd': [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    'alm_se_gate_supported': [_I, _I],
+    'alm_se_gate_fwd': [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    'alm_se_gate_bwd_ws_floats': [_I, _I, _I, _I],
+    'alm_se_gate_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    'alm_film_fwd': [_P, _P, _P, _P, _I, _I, _F, _F, _P],
+    'alm_film_bwd_ws_floats': [_I, _I],
+    'alm_film_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _P],
     'alm_memset_zero': [_P, _L, _P],
     'alm_list_op_id': [ctypes.c_char_p],
     'alm_list_op_nargs': [_I],

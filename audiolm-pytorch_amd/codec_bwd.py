@@ -6,6 +6,7 @@ mode with grad mode on and an input or parameter that requires grad; every other
 The forward of each Function runs the SAME forward kernels as the eval path (the ResidualUnit as its two alm_conv1d_causal launches, to which the
 fused alm_resunit_causal is bitwise equal, with the skip added by alm_add_f32), so a training-mode output is bitwise the eval-mode output.
 Saved per ResidualUnit: its input x, the intermediate h = ELU(conv_k7(x)) and the pre-residual y = ELU(conv_k1(h)) (DESIGN.md gives the memory).
+The squeeze-excite unit (ResidualUnitSEFn) and the FiLM conditioner (FiLMFn) run on csrc/film_se.hip the same way.
 """
 from __future__ import annotations
 
@@ -87,6 +88,56 @@ class ResidualUnitFn(torch.autograd.Function):
         dh, dw1, db1 = _conv_bwd(c1, g, y, h, ctx.needs_input_grad[0] or need7, need1)
         dx, dw7, db7 = _conv_bwd(c7, dh, h, x, ctx.needs_input_grad[0], need7, residual=g) if dh is not None else (None, None, None)
         return dx, dw7, db7, dw1, db1, None
+
+
+def se_params(se):
+    """(W1 [inner, C, 1], b1, W2 [C, inner, 1], b2) of a soundstream.SqueezeExcite as the kernels read them: the nn.Conv1d tensors themselves"""
+    c1, c2 = se.net[0], se.net[2]
+    return tuple(t.detach().to(F32).contiguous() for t in (c1.weight, c1.bias, c2.weight, c2.bias))
+
+
+class ResidualUnitSEFn(torch.autograd.Function):
+    """x + SE(ELU(conv_k1(ELU(conv_k7(x))))) (squeeze_excite=True): the eval path's three launches.  Saved: x, h = ELU(conv_k7(x)) and
+    u = ELU(conv_k1(h)), the gate's input; the cumulative mean, the hidden layer and the gate are recomputed in alm_se_gate_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, w7, b7, w1, b1, sw1, sb1, sw2, sb2, unit):
+        c7, c1 = unit.fn[0], unit.fn[2]
+        h = c7.run(x, elu=True)
+        u = c1.run(h, elu=True)
+        ctx.unit = unit
+        ctx.save_for_backward(x, h, u, w7, w1, sw1, sb1, sw2, sb2)
+        return ops.se_gate_fwd(u, *se_params(unit.fn[4]), residual=x)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, h, u = ctx.saved_tensors[:3]
+        unit = ctx.unit
+        c7, c1 = unit.fn[0], unit.fn[2]
+        g = g.to(F32).contiguous()
+        need = ctx.needs_input_grad
+        need7, need1 = need[1] or need[2], need[3] or need[4]
+        du, dsw1, dsb1, dsw2, dsb2 = ops.se_gate_bwd(g, u, *se_params(unit.fn[4]))
+        dh, dw1, db1 = _conv_bwd(c1, du, u, h, need[0] or need7, need1)
+        dx, dw7, db7 = _conv_bwd(c7, dh, h, x, need[0], need7, residual=g) if dh is not None else (None, None, None)
+        return (dx, dw7, db7, dw1, db1, dsw1 if need[5] else None, dsb1 if need[6] else None, dsw2 if need[7] else None, dsb2 if need[8] else None, None)
+
+
+class FiLMFn(torch.autograd.Function):
+    """x * gamma + beta on (b, n, dim), (gamma | beta) = to_cond(cond) formed in the kernel; saved: x"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, cond):
+        ctx.cond = cond
+        ctx.save_for_backward(x, weight, bias)
+        return ops.film_fwd(x, weight.detach().to(F32).contiguous(), bias.detach().to(F32).contiguous(), *cond)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, bias = ctx.saved_tensors
+        dx, dw, db = ops.film_bwd(g.to(F32).contiguous(), x, weight.detach().to(F32).contiguous(), bias.detach().to(F32).contiguous(), *ctx.cond)
+        need = ctx.needs_input_grad
+        return dx if need[0] else None, dw if need[1] else None, db if need[2] else None, None
 
 
 class CausalConvTranspose1dFn(torch.autograd.Function):

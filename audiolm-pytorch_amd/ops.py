@@ -1389,6 +1389,82 @@ def geglu_bct_bwd(dh, u):
     return du
 
 
+# ---- squeeze-excite of the ResidualUnit and the FiLM conditioners (csrc/film_se.hip), exact fp32, no atomics
+
+def se_gate_supported(C, inner):
+    """True iff the squeeze-excite kernels take the widths (any C >= 1, inner <= 128)"""
+    return bool(_lib.query('alm_se_gate_supported', int(C), int(inner)))
+
+
+def _se_args(u, w1, b1, w2, b2):
+    for t in (u, w1, b1, w2, b2):
+        _chk(t, F32)
+    B, C, T = u.shape
+    inner = w1.shape[0]
+    assert u.is_contiguous() and all(t.is_contiguous() for t in (w1, b1, w2, b2))
+    assert w1.numel() == inner * C and w2.numel() == C * inner and w2.shape[0] == C and b1.numel() == inner and b2.numel() == C
+    return B, C, inner, T
+
+
+def se_gate_fwd(u, w1, b1, w2, b2, *, residual=None):
+    """u fp32 [B, C, T] -> u * sigmoid(W2 silu(W1 m + b1) + b2) (+ residual), m = the cumulative mean of u over the CHANNEL axis (the reference's
+    SqueezeExcite inside a ResidualUnit); w1 [inner, C(, 1)], w2 [C, inner(, 1)]."""
+    B, C, inner, T = _se_args(u, w1, b1, w2, b2)
+    if residual is not None:
+        _chk(residual, F32)
+        assert residual.shape == u.shape and residual.is_contiguous()
+    out = _new_like(u)
+    _lib.call('alm_se_gate_fwd', u.data_ptr(), _p(residual), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(), B, C, inner, T, _st())
+    return out
+
+
+def se_gate_bwd(g, u, w1, b1, w2, b2):
+    """g = dL/dout, u (the forward input) fp32 [B, C, T] -> (du, dW1 like w1, db1, dW2 like w2, db2) of se_gate_fwd (without the residual's gradient);
+    everything but u is recomputed, the parameter gradients are summed in a fixed order in a workspace of alm_se_gate_bwd_ws_floats floats."""
+    B, C, inner, T = _se_args(u, w1, b1, w2, b2)
+    _chk(g, F32)
+    assert g.shape == u.shape and g.is_contiguous()
+    n = _lib.query('alm_se_gate_bwd_ws_floats', B, C, inner, T)
+    if n < 0:
+        raise _lib.AlmError('se_gate_bwd: widths outside the kernel envelope (inner <= 128) or a workspace past 2^31 floats')
+    ws = _new((n,), dtype=F32, device=u.device)
+    du = _new_like(u)
+    dw1, db1, dw2, db2 = _new_like(w1), _new_like(b1), _new_like(w2), _new_like(b2)
+    _lib.call('alm_se_gate_bwd', g.data_ptr(), u.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), du.data_ptr(), dw1.data_ptr(),
+              db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), ws.data_ptr(), n, B, C, inner, T, _st())
+    return du, dw1, db1, dw2, db2
+
+
+def _film_args(x, w, b):
+    _chk(x, F32), _chk(w, F32), _chk(b, F32)
+    C = x.shape[-1]
+    assert x.is_contiguous() and w.is_contiguous() and b.is_contiguous() and tuple(w.shape) == (2 * C, 2) and tuple(b.shape) == (2 * C,)
+    return x.numel() // C, C
+
+
+def film_fwd(x, w, b, cond0, cond1):
+    """x fp32 [..., C] -> x * gamma + beta, (gamma | beta) = w @ (cond0, cond1) + b with w [2 C, 2], b [2 C] (FiLM.to_cond)"""
+    rows, C = _film_args(x, w, b)
+    y = _new_like(x)
+    _lib.call('alm_film_fwd', x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), rows, C, float(cond0), float(cond1), _st())
+    return y
+
+
+def film_bwd(g, x, w, b, cond0, cond1):
+    """(dx, dW [2 C, 2], db [2 C]) of film_fwd; the column sums per row chunk in a workspace of alm_film_bwd_ws_floats floats, added in chunk order"""
+    rows, C = _film_args(x, w, b)
+    _chk(g, F32)
+    assert g.shape == x.shape and g.is_contiguous()
+    n = _lib.query('alm_film_bwd_ws_floats', rows, C)
+    if n < 0:
+        raise _lib.AlmError('film_bwd: the partial-sum workspace exceeds 2^31 floats')
+    ws = _new((n,), dtype=F32, device=x.device)
+    dx, dw, db = _new_like(x), _new_like(w), _new_like(b)
+    _lib.call('alm_film_bwd', g.data_ptr(), x.data_ptr(), w.data_ptr(), b.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), n, rows, C,
+              float(cond0), float(cond1), _st())
+    return dx, dw, db
+
+
 # ---- HuBERT feature model (csrc/hubert.hip; conv1d_valid and mha_attn are the shared fp32 kernels of csrc/dense_f32.hip) ----
 def hubert_conv0_stats(wave, w, stride, eps=1e-5):
     """wave fp32 [B, Tin] (unit element stride), w fp32 [C, k] -> stats fp32 [B, C, 2] = (mean, rstd) over time of conv1d(wave, w, stride), the

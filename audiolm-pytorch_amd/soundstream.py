@@ -6,7 +6,8 @@ decoder :347-360, 382-395, 615-627) run on the MI355X kernels of csrc/codec.hip 
 three wave MultiScaleDiscriminators, hinge / feature / reconstruction terms) are opt-in, `with_discriminators=True` (discriminators.py,
 csrc/discr.hip), and so are the ComplexSTFTDiscriminator, `stft_discriminator=True` (csrc/stft_discr.hip), and the multi-spectral mel-spectrogram
 reconstruction loss, `with_mel_loss=True` (mel_loss.py, csrc/mel_loss.hip), and the gradient penalty of the discriminator loss, `with_grad_penalty=True`
-(a double backward through the discriminator kernels); the LFQ / FSQ quantizers are out of scope and raise.  In training mode the quantizer takes one
+(a double backward through the discriminator kernels), and the FiLM conditioners of the denoising variant, `with_film=True` (`is_denoising=`;
+csrc/film_se.hip, which also holds the squeeze-excite gate of `squeeze_excite=True` units); the LFQ / FSQ quantizers are out of scope and raise.  In training mode the quantizer takes one
 training step per call (csrc/rvq_train.hip: quantize dropout, commitment loss, rotation trick, EMA codebooks with dead-code expiry, k-means
 initialisation; single process only), so `forward(x, return_recons_only=True | return_encoded=True)` is differentiable end to end.  The conv encoder / decoder are
 differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
@@ -20,6 +21,8 @@ The module tree keeps the reference's parameter / buffer NAMES for the parts it 
 `rq.*` of a reference checkpoint load with `load_state_dict(..., strict=False)`:
     encoder.0.conv.{weight,bias}                        CausalConv1d(input_channels -> channels, 7)
     encoder.{b}.{r}.fn.{0,2}.conv.{weight,bias}         ResidualUnit r of EncoderBlock b (k7 dilated conv, ELU, k1 conv, ELU, + x)
+    encoder.{b}.{r}.fn.4.net.{0,2}.{weight,bias}        its SqueezeExcite (squeeze_excite=True only; decoder units alike)
+    {encoder,decoder}_film.to_cond.{weight,bias}        FiLM conditioners (with_film=True only)
     encoder.{b}.3.conv.{weight,bias}                    strided down-sampling conv (k = 2 * stride)
     encoder.{last}.conv.{weight,bias}                   CausalConv1d(-> codebook_dim, 3)
     {encoder,decoder}_attn.layers.{i}.0.{norm.{weight,bias}, to_qkv.weight, q_scale, k_scale, attn_fn.rel_pos.inv_freq, to_v_gate.0.{weight,bias},
@@ -130,16 +133,44 @@ class CausalConvTranspose1d(nn.Module):                          # soundstream.p
         return self.run(x)
 
 
-class _ResidualFn(nn.Module):
-    """holder with the reference's `.fn` Sequential naming: fn.0 = dilated k7 conv, fn.2 = k1 conv (fn.1 / fn.3 are ELUs)."""
+class SqueezeExcite(nn.Module):                                  # soundstream.py:145-169
+    """holder of the reference's parameters (`net.0` / `net.2`: the two k = 1 convs around the SiLU).  Inside a ResidualUnit its input is (b, c, n)
+    and the reference takes the cumulative mean over dim -2, the CHANNEL axis: the op is pointwise in time and runs as
+    alm_se_gate_fwd, fused with the unit's skip add."""
 
-    def __init__(self, chan, dilation, kernel_size, pad_mode):
+    def __init__(self, dim, reduction_factor=4, dim_minimum=8):
+        super().__init__()
+        dim_inner = max(dim_minimum, dim // reduction_factor)
+        if not ops.se_gate_supported(dim, dim_inner):
+            raise NotImplementedError(f'squeeze_excite: the squeeze-excite kernels hold the hidden layer in registers, up to 128 wide (512 channels); got '
+                                      f'{dim} channels / hidden width {dim_inner}')
+        self.net = nn.Sequential(nn.Conv1d(dim, dim_inner, 1), nn.SiLU(), nn.Conv1d(dim_inner, dim, 1), nn.Sigmoid())
+
+    def forward(self, x, residual=None):
+        """x fp32 [B, C, T] -> x * gate(x) (+ residual)"""
+        if not x.is_cuda:
+            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
+        return ops.se_gate_fwd(x.to(F32).contiguous(), *codec_bwd.se_params(self), residual=residual)
+
+
+class _ResidualFn(nn.Module):
+    """holder with the reference's `.fn` Sequential naming: fn.0 = dilated k7 conv, fn.2 = k1 conv (fn.1 / fn.3 are ELUs), with squeeze_excite=True
+    fn.4 = SqueezeExcite."""
+
+    def __init__(self, chan, dilation, kernel_size, pad_mode, squeeze_excite=False):
         super().__init__()
         self.fn = nn.Sequential(CausalConv1d(chan, chan, kernel_size, dilation=dilation, pad_mode=pad_mode), nn.ELU(),
-                                CausalConv1d(chan, chan, 1, pad_mode=pad_mode), nn.ELU())
+                                CausalConv1d(chan, chan, 1, pad_mode=pad_mode), nn.ELU(), *((SqueezeExcite(chan),) if squeeze_excite else ()))
+        self.squeeze_excite = bool(squeeze_excite)
 
     def forward(self, x):                                        # soundstream.py:362-369: ELU(conv1(ELU(conv7(x)))) + x
         c7, c1 = self.fn[0], self.fn[2]
+        if self.squeeze_excite:                                  # SE(ELU(conv1(ELU(conv7(x))))) + x: the two convs, then the gate with the skip add
+            se = self.fn[4]
+            if codec_bwd.wants_grad(self, x):
+                return codec_bwd.ResidualUnitSEFn.apply(x, c7.conv.weight, c7.conv.bias, c1.conv.weight, c1.conv.bias, se.net[0].weight, se.net[0].bias,
+                                                        se.net[2].weight, se.net[2].bias, self)
+            return se(c1.run(c7.run(x, elu=True), elu=True), residual=x)
         if codec_bwd.wants_grad(self, x):                        # two launches + the skip add, h and the pre-residual output saved (bitwise the fused result)
             return codec_bwd.ResidualUnitFn.apply(x, c7.conv.weight, c7.conv.bias, c1.conv.weight, c1.conv.bias, self)
         if FUSE_RESUNIT and ops.resunit_supported(x.shape[1]) and c7.dilation * (c7.kernel_size - 1) < x.shape[2]:
@@ -150,10 +181,8 @@ class _ResidualFn(nn.Module):
 
 
 def ResidualUnit(chan_in, chan_out, dilation, kernel_size=7, squeeze_excite=False, pad_mode='reflect'):
-    if squeeze_excite:
-        raise NotImplementedError('squeeze_excite is not on the tokenize hot path (reference default False)')
     assert chan_in == chan_out
-    return _ResidualFn(chan_in, dilation, kernel_size, pad_mode)
+    return _ResidualFn(chan_in, dilation, kernel_size, pad_mode, squeeze_excite)
 
 
 def EncoderBlock(chan_in, chan_out, stride, cycle_dilations=(1, 3, 9), squeeze_excite=False, pad_mode='reflect'):   # soundstream.py:371-380
@@ -531,6 +560,27 @@ class LocalTransformer(nn.Module):
         return _btc(self.run_bct(_btc(x.to(F32).contiguous(), grad)), grad)
 
 
+class FiLM(nn.Module):                                           # soundstream.py:442-449
+    """x * gamma + beta with (gamma | beta) = to_cond(cond), cond = [is_denoising, not is_denoising]: alm_film_fwd / alm_film_bwd (gamma and beta
+    are formed in the kernel from to_cond's weight and bias)"""
+
+    def __init__(self, dim, dim_cond=2):
+        super().__init__()
+        if dim_cond != 2:
+            raise NotImplementedError('FiLM: only the reference\'s dim_cond=2 (the denoising switch) is implemented')
+        self.to_cond = nn.Linear(dim_cond, dim * 2)
+
+    def forward(self, x, cond):
+        """x fp32 (b, n, dim), cond = a pair of floats -> same shape"""
+        if not x.is_cuda:
+            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
+        x = x.to(F32).contiguous()
+        cond = (float(cond[0]), float(cond[1]))
+        if codec_bwd.wants_grad(self, x):
+            return codec_bwd.FiLMFn.apply(x, self.to_cond.weight, self.to_cond.bias, cond)
+        return ops.film_fwd(x, self.to_cond.weight.detach().to(F32).contiguous(), self.to_cond.bias.detach().to(F32).contiguous(), *cond)
+
+
 def curtail_to_multiple(t, mult, from_left=False):               # soundstream.py:86-90
     data_len = t.shape[-1]
     rounded = (data_len // mult) * mult
@@ -541,7 +591,9 @@ class SoundStream(nn.Module):
     """Constructor keywords and defaults follow the reference (soundstream.py:451-510); options outside the tokenize path raise.  The training losses
     are opt-in switches of this port: `with_discriminators=True` (wave discriminators and loss branches), on top of it `stft_discriminator=True`,
     `with_mel_loss=True` and `with_grad_penalty=True` (lets `forward(..., return_discr_loss=True, apply_grad_penalty=True)` add the reference's
-    gradient penalties; registers no parameter, buffer or child module, so the state_dict is the same with and without it)."""
+    gradient penalties; registers no parameter, buffer or child module, so the state_dict is the same with and without it) and, independent of
+    those, `with_film=True` (registers the reference's `encoder_film` / `decoder_film` and lets `forward(..., target=, is_denoising=)` apply them;
+    without discriminators together with a codec-only return: the inference use of the denoiser)."""
 
     def __init__(self, *, channels=32, strides=(2, 4, 5, 8), channel_mults=(2, 4, 8, 16), codebook_dim=512, codebook_size=None,
                  finite_scalar_quantizer_levels=None, rq_num_quantizers=8, rq_commitment_weight=1., rq_ema_decay=0.95,
@@ -552,12 +604,12 @@ class SoundStream(nn.Module):
                  attn_xpos_scale_base=None, attn_dynamic_pos_bias=False, use_gate_loop_layers=False, squeeze_excite=False, pad_mode='reflect',
                  stft_discriminator=None, with_discriminators=False, stft_normalized=False, complex_stft_discr_logits_abs=True,
                  complex_stft_discr_kwargs: dict = {}, with_mel_loss=False, multi_spectral_window_powers_of_two=tuple(range(6, 12)),
-                 multi_spectral_n_ffts=512, multi_spectral_n_mels=64, with_grad_penalty=False, **kwargs):
+                 multi_spectral_n_ffts=512, multi_spectral_n_mels=64, with_grad_penalty=False, with_film=False, **kwargs):
         super().__init__()
         if use_lookup_free_quantizer or use_finite_scalar_quantizer or finite_scalar_quantizer_levels is not None:
             raise NotImplementedError('LFQ / FSQ quantizers are out of scope (SURVEY.md §2)')
-        if use_gate_loop_layers or squeeze_excite or rq_stochastic_sample_codes:
-            raise NotImplementedError('gate-loop layers / squeeze-excite / stochastic code sampling are not on the tokenize hot path')
+        if use_gate_loop_layers or rq_stochastic_sample_codes:
+            raise NotImplementedError('gate-loop layers / stochastic code sampling are not implemented (reference defaults False)')
         assert codebook_size is not None, '`codebook_size` must be set'
         self.target_sample_hz = target_sample_hz
         self.single_channel = input_channels == 1
@@ -571,6 +623,12 @@ class SoundStream(nn.Module):
                            xpos_scale_base=attn_xpos_scale_base, dynamic_pos_bias=attn_dynamic_pos_bias, prenorm=True, causal=True)   # soundstream.py:533-543
         self.encoder_attn = LocalTransformer(**attn_kwargs) if use_local_attn else None
         self.decoder_attn = LocalTransformer(**attn_kwargs) if use_local_attn else None
+        # the FiLM conditioners of the denoising variant (soundstream.py:547, 611) are opt-in: without `with_film=True` nothing is registered and
+        # `is_denoising` raises, like before; with it a reference checkpoint's `encoder_film.*` / `decoder_film.*` load strictly
+        self.with_film = bool(with_film)
+        if self.with_film:
+            self.encoder_film = FiLM(codebook_dim, dim_cond=2)
+            self.decoder_film = FiLM(codebook_dim, dim_cond=2)
         dec_cycle_dilations = kwargs.pop('dec_cycle_dilations', (1, 3, 9))          # remaining kwargs: attention / discriminator / loss options of
                                                                                     # the parts that are not built here (ignored, like before)
         dblocks = [DecoderBlock(co, ci, s, dec_cycle_dilations, squeeze_excite, pad_mode) for (ci, co), s in reversed(tuple(zip(pairs, strides)))]
@@ -633,10 +691,12 @@ class SoundStream(nn.Module):
     def device(self):
         return next(self.parameters()).device
 
-    def non_discr_parameters(self):                              # soundstream.py:760-769 (the FiLM conditioners do not exist here)
+    def non_discr_parameters(self):                              # soundstream.py:760-769 (the FiLM conditioners: with `with_film=True` only)
         return [*self.encoder.parameters(), *self.decoder.parameters(),
                 *(self.encoder_attn.parameters() if self.encoder_attn is not None else []),
-                *(self.decoder_attn.parameters() if self.decoder_attn is not None else []), *self.rq.parameters()]
+                *(self.decoder_attn.parameters() if self.decoder_attn is not None else []),
+                *(self.encoder_film.parameters() if self.with_film else []), *(self.decoder_film.parameters() if self.with_film else []),
+                *self.rq.parameters()]
 
     @property
     def seq_len_multiple_of(self):                               # soundstream.py:772-774
@@ -690,12 +750,15 @@ class SoundStream(nn.Module):
         apply_grad_penalty), with
         return_loss_breakdown also (recon, multi_spectral, adversarial, feature, commitment).  `target=` replaces the input in the recon term."""
         codec_only = return_encoded or return_codes_only or return_recons_only
-        if not self.with_discriminators and (target is not None or is_denoising is not None or return_discr_loss or return_discr_losses_separately
+        denoising_args = (target is not None or is_denoising is not None) and not self.with_film        # with_film: the inference use of the denoiser
+        if not self.with_discriminators and (denoising_args or return_discr_loss or return_discr_losses_separately
                                              or return_loss_breakdown or apply_grad_penalty or not codec_only):
             raise NotImplementedError('only forward(..., return_codes_only=True | return_encoded=True | return_recons_only=True) is implemented '
                                       'on a SoundStream built without with_discriminators=True (the training losses are opt-in)')
-        if is_denoising is not None:
-            raise NotImplementedError('is_denoising (the FiLM conditioners of the denoising variant) is not implemented')
+        if is_denoising is not None and not self.with_film:
+            raise NotImplementedError('is_denoising (the FiLM conditioners of the denoising variant) is opt-in: construct the SoundStream with with_film=True')
+        assert not (is_denoising is not None and target is None), '`is_denoising` needs `target` (soundstream.py:817)'
+        denoise_input = None if is_denoising is None else (float(bool(is_denoising)), float(not is_denoising))     # [1, 0] denoise, [0, 1] not
         if not codec_only:
             self._check_loss_options(apply_grad_penalty)
         with torch.set_grad_enabled(torch.is_grad_enabled() and self.training):
@@ -704,12 +767,16 @@ class SoundStream(nn.Module):
                 for transform in self.mel_spec_transforms:       # a clip too short for a scale's reflect padding: by name, before the codec's launches
                     transform.check_length(x.shape[-1])
             feats = self.encode(x)
+            if denoise_input is not None:                        # soundstream.py:835-837: after encoder_attn, before the quantizer
+                feats = self.encoder_film(feats, denoise_input)
             quantized, indices, commit_loss = self.rq(feats)
             if return_codes_only:
                 return indices                                       # (g, b, n, q), soundstream.py:847-848
             b, n = indices.shape[1], indices.shape[2]
             if return_encoded:
                 return quantized, indices.permute(1, 2, 0, 3).reshape(b, n, -1), commit_loss          # 'g b n q -> b n (g q)', :851
+            if denoise_input is not None:                        # :854-855: after the quantizer, before decoder_attn (decode() itself never applies it)
+                quantized = self.decoder_film(quantized, denoise_input)
             recon = self.decode(quantized)                           # :857-866, unpack(recon_x, ps, '* c n')
             if return_recons_only:
                 return recon.reshape(*lead, recon.shape[-2], recon.shape[-1])

@@ -682,6 +682,29 @@ int alm_mel_frame_loss_fwd(const float* mel, float* norms, float* loss, float* m
 int alm_mel_frame_loss_bwd(const float* mel, const float* norms, const float* gout, float* dmel, int Bh, int n_mels, int T, float alpha, void* stream);
 int alm_mel_power_bwd(const float* dmel, const float* fb, const float* X, float* dX, int B, int F, int T, int n_mels, void* stream);
 
+/* ---- the denoising SoundStream: squeeze-excite inside the ResidualUnit and the FiLM conditioners (csrc/film_se.hip), exact fp32, no atomics ------
+ * SqueezeExcite (reference soundstream.py:145-169) as the ResidualUnit applies it: per column (b, t) of u [B][C][T] the cumulative mean over the
+ * CHANNEL axis, m[c] = (u[0] + .. + u[c]) / (c + 1), then gate = sigmoid(W2 silu(W1 m + b1) + b2) with W1 [inner][C], W2 [C][inner] (the nn.Conv1d
+ * k = 1 weights as they are) and out = u * gate (+ residual [B][C][T] if given).
+ *   alm_se_gate_supported(C, inner) = 1 iff C >= 1 and 1 <= inner <= 128; anything else is ALM_ERR_UNSUPPORTED.
+ *   alm_se_gate_bwd : from g = dL/dout and the forward input u (everything else is recomputed): du [B][C][T] (the skip's gradient is the caller's),
+ *                     dW1 [inner][C], db1 [inner], dW2 [C][inner], db2 [C].  The parameter gradients are alm_conv1d_wgrad (k = 1) over operands left
+ *                     in ws: per-chunk partials summed in chunk order, bitwise reproducible.  ws: alm_se_gate_bwd_ws_floats floats, owned by the
+ *                     caller (-1: outside the envelope or past 2^31).
+ * FiLM (soundstream.py:442-449) on x [rows][C]: y = x * gamma + beta, (gamma | beta)[i] = W[i][0] cond0 + W[i][1] cond1 + b[i], W [2 C][2], b [2 C].
+ *   alm_film_bwd : dx = g * gamma, dW [2 C][2] and db [2 C] from dgamma = sum_r g x, dbeta = sum_r g: per-row-chunk partials in ws
+ *                  (alm_film_bwd_ws_floats floats, owned by the caller), summed in chunk order. */
+int alm_se_gate_supported(int C, int inner);
+int alm_se_gate_fwd(const float* u, const float* residual, const float* W1, const float* b1, const float* W2, const float* b2, float* out, int B, int C,
+                    int inner, int T, void* stream);
+int alm_se_gate_bwd_ws_floats(int B, int C, int inner, int T);
+int alm_se_gate_bwd(const float* g, const float* u, const float* W1, const float* b1, const float* W2, const float* b2, float* du, float* dW1, float* db1,
+                    float* dW2, float* db2, float* ws, long long ws_floats, int B, int C, int inner, int T, void* stream);
+int alm_film_fwd(const float* x, const float* W, const float* b, float* y, int rows, int C, float cond0, float cond1, void* stream);
+int alm_film_bwd_ws_floats(int rows, int C);
+int alm_film_bwd(const float* g, const float* x, const float* W, const float* b, float* dx, float* dW, float* db, float* ws, long long ws_floats, int rows,
+                 int C, float cond0, float cond1, void* stream);
+
 /* ---- launch lists (round 6): a recorded sequence of the launches above re-issued by ONE host call ---------------------------------------------
  * The depth loop of audiolm_pytorch.py:528-547 (Transformer.forward) and its backward are ~190 launches per training step whose ORDER and scalar arguments
  * depend only on the model configuration and the batch shape; only buffer addresses change between steps.  The host records the sequence once per shape

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty] [se_film]"""
 import os
 import sys
 import time
@@ -996,6 +996,67 @@ def bench_grad_penalty():
     except Exception as e:                                       # the yardstick is optional: say so and keep the native numbers
         t_o, = median([lambda: wave_penalties(True)])
         print(f'grad_penalty {B} x {n}: wave discriminators\' penalties alone: hand {t_o:.2f} ms   ATen did not run ({type(e).__name__}: {e})', flush=True)
+
+
+def bench_se_film():
+    """Squeeze-excite of the ResidualUnit and the FiLM conditioners (csrc/film_se.hip) at the default codec's unit shapes (8 x 10 s @ 16 kHz:
+    C = 32 / 64 / 128 / 256 at T = 160000 / 80000 / 20000 / 4000, hidden width max(8, C / 4)): the gate's forward and backward launches with the
+    rate on the bytes the op must move (12 B per element: u, residual, out; g, u, du), and beside them, same box and same run, a whole unit without
+    and with squeeze-excite: eval forward, and training forward + backward.  Interleaved rounds, medians, one event pair per call."""
+    from audiolm_pytorch_amd import soundstream as S
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def median(fns, rounds=7, warm=2):
+        for _ in range(warm):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(rounds):
+            for t, fn in zip(ts, fns):
+                t.append(once(fn))
+        return [sorted(t)[len(t) // 2] for t in ts]
+
+    torch.manual_seed(0)
+    B, n = 8, 160000
+    print(f'{"shape":28s} {"se fwd":>8s} {"GB/s":>6s} {"se bwd":>8s} {"GB/s":>6s} | {"unit fwd":>9s} {"+SE":>8s} {"ratio":>6s} | {"unit f+b":>9s} {"+SE":>8s} {"ratio":>6s}',
+          flush=True)
+    for C, T in ((32, n), (64, n // 2), (128, n // 8), (256, n // 40)):
+        inner = max(8, C // 4)
+        u, res, g = (torch.randn(B, C, T, device=dev) for _ in range(3))
+        w1, b1 = torch.randn(inner, C, 1, device=dev) * C ** -0.5, torch.randn(inner, device=dev) * 0.1
+        w2, b2 = torch.randn(C, inner, 1, device=dev) * inner ** -0.5, torch.randn(C, device=dev) * 0.1
+        t_f, t_b = median([lambda: ops.se_gate_fwd(u, w1, b1, w2, b2, residual=res), lambda: ops.se_gate_bwd(g, u, w1, b1, w2, b2)])
+        gb = 12.0 * u.numel() / 1e6                               # MB per launch on the minimum traffic; / ms = GB/s
+        plain, se = (S.ResidualUnit(C, C, 3, squeeze_excite=flag).to(dev) for flag in (False, True))
+        ug = u.detach().requires_grad_()
+
+        def fwd(unit):
+            with torch.no_grad():
+                return unit.eval()(u)
+
+        def step(unit):
+            unit.train().zero_grad(set_to_none=True)
+            ug.grad = None
+            unit(ug).backward(g)                                  # the input gradient too, as inside the stack
+
+        f0, f1 = median([lambda: fwd(plain), lambda: fwd(se)])
+        s0, s1 = median([lambda: step(plain), lambda: step(se)], rounds=5)
+        print(f'{f"C={C} inner={inner} T={T}":28s} {t_f:8.3f} {gb / t_f:6.0f} {t_b:8.3f} {gb / t_b:6.0f} | {f0:9.3f} {f1:8.3f} {f1 / f0:6.2f} | '
+              f'{s0:9.3f} {s1:8.3f} {s1 / s0:6.2f}', flush=True)
+        del u, ug, res, g, plain, se
+    rows, C = 8 * 500, 512                                        # the default codebook_dim at 8 x 10 s
+    x, gy = torch.randn(rows, C, device=dev), torch.randn(rows, C, device=dev)
+    w, b = torch.randn(2 * C, 2, device=dev), torch.randn(2 * C, device=dev)
+    t_f, t_b = median([lambda: ops.film_fwd(x, w, b, 1., 0.), lambda: ops.film_bwd(gy, x, w, b, 1., 0.)])
+    print(f'film [{rows} x {C}]: fwd {t_f * 1e3:.1f} us   bwd (2 launches) {t_b * 1e3:.1f} us', flush=True)
 
 
 if __name__ == '__main__':
