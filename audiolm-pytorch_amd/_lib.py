@@ -200,6 +200,11 @@ SIGNATURES = {
     'alm_film_fwd': [_P, _P, _P, _P, _I, _I, _F, _F, _P],
     'alm_film_bwd_ws_floats': [_I, _I],
     'alm_film_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _P],
+    'alm_fsq_consts_floats': [_I],
+    'alm_fsq_fwd': [_P, _L, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _P],
+    'alm_fsq_decode': [_P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    'alm_fsq_bwd_ws_floats': [_I, _I, _I],
+    'alm_fsq_bwd': [_P, _L, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     'alm_memset_zero': [_P, _L, _P],
     'alm_list_op_id': [ctypes.c_char_p],
     'alm_list_op_nargs': [_I],

@@ -6,7 +6,8 @@ mode with grad mode on and an input or parameter that requires grad; every other
 The forward of each Function runs the SAME forward kernels as the eval path (the ResidualUnit as its two alm_conv1d_causal launches, to which the
 fused alm_resunit_causal is bitwise equal, with the skip added by alm_add_f32), so a training-mode output is bitwise the eval-mode output.
 Saved per ResidualUnit: its input x, the intermediate h = ELU(conv_k7(x)) and the pre-residual y = ELU(conv_k1(h)) (DESIGN.md gives the memory).
-The squeeze-excite unit (ResidualUnitSEFn) and the FiLM conditioner (FiLMFn) run on csrc/film_se.hip the same way.
+The squeeze-excite unit (ResidualUnitSEFn) and the FiLM conditioner (FiLMFn) run on csrc/film_se.hip the same way, the residual finite scalar
+quantizer (FsqFn) on csrc/fsq.hip.
 """
 from __future__ import annotations
 
@@ -203,6 +204,43 @@ class RvqTrainFn(torch.autograd.Function):
             coef = (g_losses[gi].to(F32) * (2. * weight / (M * dg))).contiguous()          # d loss_q / d r = 2 w (r - quant) / (M d)
             ops.rvq_train_bwd(x[:, gi * dg:(gi + 1) * dg], idx[gi], E, g_out[:, gi * dg:(gi + 1) * dg], coef, dx[:, gi * dg:(gi + 1) * dg], rotation)
         return dx, None, None
+
+
+class FsqFn(torch.autograd.Function):
+    """the grouped residual FSQ (soundstream.GroupedResidualFSQ.run): x [M, dim] -> (out, indices; the indices carry no gradient).  `params`: per
+    group project_in.{weight, bias}, project_out.{weight, bias} (nothing in the identity case).  Saved: x, per group the projected input z [M, d] and
+    the parameters; the chain is recomputed in alm_fsq_bwd, whose straight-through rounding and detached residual leave one direct path."""
+
+    @staticmethod
+    def forward(ctx, x, mod, k, *params):
+        out, idx, zs = mod.run(x, k, save_z=True)
+        ctx.mod, ctx.k = mod, k
+        ctx.have_z = [z is not None for z in zs]
+        ctx.save_for_backward(x, *[z for z in zs if z is not None], *params)
+        ctx.mark_non_differentiable(idx)
+        return out, idx
+
+    @staticmethod
+    def backward(ctx, g_out, _):
+        mod, k = ctx.mod, ctx.k
+        x, *rest = ctx.saved_tensors
+        nz = sum(ctx.have_z)
+        zs, params = rest[:nz], rest[nz:]
+        M, dim = x.shape
+        dg, d, Q = dim // mod.groups, len(mod.levels), mod.num_quantizers
+        g_out = g_out.to(F32).contiguous()
+        dx = torch.empty_like(x)
+        consts = mod._consts(x.device)
+        grads = []
+        for g in range(mod.groups):
+            sl = slice(g * dg, (g + 1) * dg)
+            if ctx.have_z[g]:
+                weights = mod.kernel_weights(params[4 * g:4 * g + 4])
+                grads.extend(ops.fsq_bwd(g_out[:, sl], x[:, sl], zs[g], weights, consts, d, Q, k, dx[:, sl]))
+            else:
+                ops.fsq_bwd(g_out[:, sl], x[:, sl], None, None, consts, d, Q, k, dx[:, sl])
+        need = ctx.needs_input_grad
+        return (dx if need[0] else None, None, None, *[gr if need[3 + i] else None for i, gr in enumerate(grads)])
 
 
 # ---------------------------------------------------------------------------------------------- LocalTransformer (csrc/local_attn_bwd.hip)

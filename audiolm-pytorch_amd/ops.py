@@ -1465,6 +1465,101 @@ def film_bwd(g, x, w, b, cond0, cond1):
     return dx, dw, db
 
 
+# ---- residual finite scalar quantization (csrc/fsq.hip), fp32, no atomics.  One call serves one group: x / out / g / dx are [M, dim_g] views with unit
+# element stride (a column slice of a wider matrix is fine); weights = (W_in [d, dim_g], b_in [d], W_out [dim_g, d], b_out [dim_g]) or None (identity)
+
+# The three places where the FSQ paper (arXiv 2309.15505, Appendix A) and vector-quantize-pytorch's FSQ differ; tests/fsq_restated.py names the same
+# three, and a check against the installed package is a change of these lines.
+FSQ_EPS = 1e-3
+FSQ_HALF_L_SIGN = +1                   # half_l = (L - 1) * (1 + FSQ_HALF_L_SIGN * FSQ_EPS) / 2
+FSQ_SHIFT_FORM = 'atanh'               # shift = atanh(offset / half_l)   ('tan': the paper's listing)
+
+FSQ_MAX_LEVELS, FSQ_MAX_DIM, FSQ_MAX_QUANTIZERS = 8, 1024, 32
+_FSQ_ROWS = dict(half_l=0, offset=1, shift=2, inv_half_w=3, half_w=4, basis=5, levels=6)
+
+
+def fsq_constants(levels, num_quantizers):
+    """the kernels' constant table, fp32 [56 + 16 Q] on the CPU: 7 rows of 8 (half_l, offset, shift, 1 / half_w, half_w, basis, levels; entry j < d
+    used, the rest 1) then scale [Q, 8] = (L - 1) ** -q and 1 / scale [Q, 8].  Computed in float64 and rounded once."""
+    levels = [int(l) for l in levels]
+    d, Q = len(levels), int(num_quantizers)
+    assert 1 <= d <= FSQ_MAX_LEVELS and 1 <= Q <= FSQ_MAX_QUANTIZERS and all(l >= 2 for l in levels)
+    L = torch.tensor(levels, dtype=torch.float64)
+    half_l = (L - 1) * (1 + FSQ_HALF_L_SIGN * FSQ_EPS) / 2
+    offset = torch.where(L % 2 == 0, 0.5, 0.).to(torch.float64)
+    shift = torch.atanh(offset / half_l) if FSQ_SHIFT_FORM == 'atanh' else torch.tan(offset / half_l)
+    half_w = torch.floor(L / 2)
+    basis = torch.cumprod(torch.cat([torch.ones(1, dtype=torch.float64), L[:-1]]), dim=0)
+    head = torch.ones(7, 8, dtype=torch.float64)
+    for name, v in (('half_l', half_l), ('offset', offset), ('shift', shift), ('inv_half_w', 1 / half_w), ('half_w', half_w), ('basis', basis),
+                    ('levels', L)):
+        head[_FSQ_ROWS[name], :d] = v
+    scale = torch.ones(Q, 8, dtype=torch.float64)
+    scale[:, :d] = (L - 1)[None, :] ** -torch.arange(Q, dtype=torch.float64)[:, None]
+    table = torch.cat([head.reshape(-1), scale.reshape(-1), (1 / scale).reshape(-1)]).to(F32)
+    assert table.numel() == _lib.query('alm_fsq_consts_floats', Q)
+    return table
+
+
+def _fsq_args(mat, weights, consts, d, Q):
+    _chk(mat, F32), _chk(consts, F32)
+    M, dim_g = mat.shape
+    assert mat.stride(1) == 1 and consts.is_contiguous() and consts.numel() == 56 + 16 * Q
+    if weights is None:
+        assert dim_g == d, 'the identity case needs dim_g == len(levels)'
+        return M, dim_g, (None,) * 4
+    w_in, b_in, w_out, b_out = weights
+    for t in weights:
+        _chk(t, F32)
+        assert t.is_contiguous()
+    assert tuple(w_in.shape) == (d, dim_g) and tuple(b_in.shape) == (d,) and tuple(w_out.shape) == (dim_g, d) and tuple(b_out.shape) == (dim_g,)
+    return M, dim_g, tuple(weights)
+
+
+def fsq_fwd(x, weights, consts, d, Q, k, idx_out, out, save_z=False):
+    """x [M, dim_g] view -> idx_out int64 [M, Q] view (-1 past layer k) and out [M, dim_g] view, both written in place; returns z float64 [M, d] (the
+    projected input in the precision the chain runs in, what fsq_bwd needs) with save_z, else None (alm_fsq_fwd)"""
+    M, dim_g, (w_in, b_in, w_out, b_out) = _fsq_args(x, weights, consts, d, Q)
+    _chk(out, F32), _chk(idx_out, torch.int64)
+    assert tuple(out.shape) == (M, dim_g) and out.stride(1) == 1 and tuple(idx_out.shape) == (M, Q) and idx_out.stride(1) == 1
+    z = _new((M, d), dtype=torch.float64, device=x.device) if save_z else None
+    _lib.call('alm_fsq_fwd', x.data_ptr(), x.stride(0), _p(w_in), _p(b_in), _p(w_out), _p(b_out), consts.data_ptr(), idx_out.data_ptr(), idx_out.stride(0),
+              out.data_ptr(), out.stride(0), _p(z), M, dim_g, d, Q, int(k), _st())
+    return z
+
+
+def fsq_decode(idx, weights, consts, d, Q, out):
+    """idx int64 [M, q <= Q] view (negative = no code) -> out [M, dim_g] view, written in place (alm_fsq_decode)"""
+    M, dim_g, (_, _, w_out, b_out) = _fsq_args(out, weights, consts, d, Q)
+    _chk(idx, torch.int64)
+    assert idx.dim() == 2 and idx.shape[0] == M and 1 <= idx.shape[1] <= Q and idx.stride(1) == 1
+    _lib.call('alm_fsq_decode', idx.data_ptr(), idx.stride(0), _p(w_out), _p(b_out), consts.data_ptr(), out.data_ptr(), out.stride(0), M, dim_g, d, Q,
+              idx.shape[1], _st())
+    return out
+
+
+def fsq_bwd(g, x, z, weights, consts, d, Q, k, dx):
+    """g = dL/dout, x [M, dim_g] views, z [M, d] from fsq_fwd (None in the identity case) -> dx view written in place; returns (dW_in, db_in, dW_out,
+    db_out), or () in the identity case.  The parameter gradients are per-row-chunk partials in a workspace of alm_fsq_bwd_ws_floats floats, added in
+    chunk order by a second launch."""
+    M, dim_g, (w_in, _, w_out, _) = _fsq_args(x, weights, consts, d, Q)
+    _chk(g, F32), _chk(dx, F32)
+    assert tuple(g.shape) == (M, dim_g) and g.stride(1) == 1 and tuple(dx.shape) == (M, dim_g) and dx.stride(1) == 1
+    grads, ws, n = (), None, 0
+    if weights is not None:
+        _chk(z, torch.float64)
+        assert z.is_contiguous() and tuple(z.shape) == (M, d)
+        n = _lib.query('alm_fsq_bwd_ws_floats', M, dim_g, d)
+        if n < 0:
+            raise _lib.AlmError('fsq_bwd: outside the kernel limits or a workspace past 2^31 floats')
+        ws = _new((n,), dtype=F32, device=x.device)
+        grads = tuple(_new_like(t) for t in weights)
+    dw_in, db_in, dw_out, db_out = grads if grads else (None,) * 4
+    _lib.call('alm_fsq_bwd', g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0), _p(z), _p(w_in), _p(w_out), consts.data_ptr(), dx.data_ptr(),
+              dx.stride(0), _p(dw_in), _p(db_in), _p(dw_out), _p(db_out), _p(ws), n, M, dim_g, d, Q, int(k), _st())
+    return grads
+
+
 # ---- HuBERT feature model (csrc/hubert.hip; conv1d_valid and mha_attn are the shared fp32 kernels of csrc/dense_f32.hip) ----
 def hubert_conv0_stats(wave, w, stride, eps=1e-5):
     """wave fp32 [B, Tin] (unit element stride), w fp32 [C, k] -> stats fp32 [B, C, 2] = (mean, rstd) over time of conv1d(wave, w, stride), the

@@ -7,7 +7,7 @@ three wave MultiScaleDiscriminators, hinge / feature / reconstruction terms) are
 csrc/discr.hip), and so are the ComplexSTFTDiscriminator, `stft_discriminator=True` (csrc/stft_discr.hip), and the multi-spectral mel-spectrogram
 reconstruction loss, `with_mel_loss=True` (mel_loss.py, csrc/mel_loss.hip), and the gradient penalty of the discriminator loss, `with_grad_penalty=True`
 (a double backward through the discriminator kernels), and the FiLM conditioners of the denoising variant, `with_film=True` (`is_denoising=`;
-csrc/film_se.hip, which also holds the squeeze-excite gate of `squeeze_excite=True` units); the LFQ / FSQ quantizers are out of scope and raise.  In training mode the quantizer takes one
+csrc/film_se.hip, which also holds the squeeze-excite gate of `squeeze_excite=True` units); the finite scalar quantizer, `use_finite_scalar_quantizer=True` (GroupedResidualFSQ, csrc/fsq.hip); the LFQ quantizer is out of scope and raises.  In training mode the quantizer takes one
 training step per call (csrc/rvq_train.hip: quantize dropout, commitment loss, rotation trick, EMA codebooks with dead-code expiry, k-means
 initialisation; single process only), so `forward(x, return_recons_only=True | return_encoded=True)` is differentiable end to end.  The conv encoder / decoder are
 differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
@@ -29,6 +29,7 @@ The module tree keeps the reference's parameter / buffer NAMES for the parts it 
                                          to_out.weight}   LocalMHA;   .layers.{i}.1.{0.{weight,bias}, 1.weight, 4.weight}   FeedForward
     decoder.0.conv / decoder.{b}.0.conv (ConvTranspose1d) / decoder.{b}.{1,2,3}.fn.{0,2}.conv / decoder.{last}.conv
     rq.rvqs.{g}.layers.{q}._codebook.{initted, cluster_size, embed_avg, embed (1, C, d)}
+    rq.rvqs.{g}.{project_in,project_out}.{weight,bias}    GroupedResidualFSQ (use_finite_scalar_quantizer=True only; nothing in the identity case)
 """
 from __future__ import annotations
 
@@ -396,6 +397,103 @@ class GroupedResidualVQ(nn.Module):
         return out.view(b, n, self.dim)
 
 
+class _ResidualFSQ(nn.Module):
+    def __init__(self, dim, codebook_dim):
+        super().__init__()
+        self.project_in = nn.Linear(dim, codebook_dim) if dim != codebook_dim else nn.Identity()
+        self.project_out = nn.Linear(codebook_dim, dim) if dim != codebook_dim else nn.Identity()
+
+
+class GroupedResidualFSQ(nn.Module):
+    """Residual finite scalar quantization (arXiv 2309.15505) in the grouped form of vector-quantize-pytorch's GroupedResidualFSQ, as the reference
+    builds it (soundstream.py:578-586).  The arithmetic is RESTATED from the paper's Appendix A and the package's residual form (tests/fsq_restated.py;
+    parity with the installed package is unpinned, like LocalMHA): per group a projection to len(levels) dimensions, Q layers of bounded rounding of
+    the scaled residual, a projection back.  No codebook state, no auxiliary loss: one alm_fsq_fwd launch per group, alm_fsq_decode for
+    `get_output_from_indices`, and in training mode with a graph wanted codec_bwd.FsqFn (alm_fsq_bwd).  rvqs.{g}.project_in / project_out are
+    nn.Linear, or nn.Identity when dim / groups == len(levels).  Quantize dropout (training mode only) is GroupedResidualVQ.dropout_index."""
+
+    def __init__(self, *, dim, levels, num_quantizers, groups=1, quantize_dropout=True, quantize_dropout_cutoff_index=1, quantize_dropout_multiple_of=1):
+        super().__init__()
+        levels = [int(l) for l in levels]
+        assert dim % groups == 0 and num_quantizers >= 1 and len(levels) >= 1 and all(l >= 2 for l in levels)
+        assert quantize_dropout_cutoff_index >= 0 and quantize_dropout_multiple_of >= 1
+        dg = dim // groups
+        if len(levels) > ops.FSQ_MAX_LEVELS:
+            raise NotImplementedError(f'GroupedResidualFSQ: len(levels) = {len(levels)} exceeds the kernels\' limit of {ops.FSQ_MAX_LEVELS}')
+        if dg > ops.FSQ_MAX_DIM:
+            raise NotImplementedError(f'GroupedResidualFSQ: dim / groups = {dg} exceeds the kernels\' limit of {ops.FSQ_MAX_DIM}')
+        if num_quantizers > ops.FSQ_MAX_QUANTIZERS:
+            raise NotImplementedError(f'GroupedResidualFSQ: num_quantizers = {num_quantizers} exceeds the kernels\' limit of {ops.FSQ_MAX_QUANTIZERS}')
+        self.codebook_size = functools.reduce(lambda a, b: a * b, levels)
+        if self.codebook_size > 1 << 24:
+            raise NotImplementedError(f'GroupedResidualFSQ: codebook_size = prod(levels) = {self.codebook_size} exceeds 2^24 (the index basis is fp32)')
+        self.dim, self.levels, self.groups, self.num_quantizers = dim, levels, groups, num_quantizers
+        self.quantize_dropout = quantize_dropout and num_quantizers > 1
+        self.quantize_dropout_cutoff_index, self.quantize_dropout_multiple_of = quantize_dropout_cutoff_index, quantize_dropout_multiple_of
+        self.rvqs = nn.ModuleList([_ResidualFSQ(dg, len(levels)) for _ in range(groups)])
+        self.constants = ops.fsq_constants(levels, num_quantizers)           # host table (fp32, CPU); a plain attribute: the state_dict has no entry for it
+        self._constants_on = {}
+
+    dropout_index = GroupedResidualVQ.dropout_index
+
+    def _consts(self, device):
+        if device not in self._constants_on:
+            self._constants_on[device] = self.constants.to(device)
+        return self._constants_on[device]
+
+    def group_params(self, g):
+        """[project_in.weight, project_in.bias, project_out.weight, project_out.bias] of group g, or [] in the identity case"""
+        r = self.rvqs[g]
+        return [] if isinstance(r.project_in, nn.Identity) else [r.project_in.weight, r.project_in.bias, r.project_out.weight, r.project_out.bias]
+
+    @staticmethod
+    def kernel_weights(params):
+        return tuple(p.detach().to(F32).contiguous() for p in params) if params else None
+
+    def run(self, x2, k, save_z=False):
+        """x2 fp32 [M, dim], k = last active layer -> (out [M, dim], idx int64 [g, M, Q] (-1 past k), per group z [M, d] or None)"""
+        M, dim = x2.shape
+        dg, d, Q = dim // self.groups, len(self.levels), self.num_quantizers
+        out = torch.empty((M, dim), dtype=F32, device=x2.device)
+        idx = torch.empty((self.groups, M, Q), dtype=torch.int64, device=x2.device)
+        consts = self._consts(x2.device)
+        zs = []
+        for g in range(self.groups):
+            weights = self.kernel_weights(self.group_params(g))
+            zs.append(ops.fsq_fwd(x2[:, g * dg:(g + 1) * dg], weights, consts, d, Q, k, idx[g], out[:, g * dg:(g + 1) * dg],
+                                  save_z=save_z and weights is not None))
+        return out, idx, zs
+
+    def forward(self, x):
+        """x fp32 (b, n, dim) -> (quantized (b, n, dim), indices (g, b, n, q) int64; -1 on the layers quantize dropout left out)"""
+        if not x.is_cuda:
+            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
+        b, n, dim = x.shape
+        assert dim == self.dim
+        x2 = x.reshape(b * n, dim).to(F32).contiguous()
+        k = self.dropout_index() if self.training else self.num_quantizers - 1
+        if codec_bwd.wants_grad(self, x2):
+            out, idx = codec_bwd.FsqFn.apply(x2, self, k, *[p for g in range(self.groups) for p in self.group_params(g)])
+        else:
+            out, idx, _ = self.run(x2.detach(), k)
+        return out.view(b, n, dim), idx.view(self.groups, b, n, self.num_quantizers)
+
+    @torch.no_grad()
+    def get_output_from_indices(self, indices):
+        """indices int (g, b, n, q <= Q) (-1 = no code) -> (b, n, dim): per group project_out of the summed codes (alm_fsq_decode)"""
+        g, b, n, q = indices.shape
+        assert g == self.groups and 1 <= q <= self.num_quantizers
+        if not indices.is_cuda:
+            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
+        dg = self.dim // self.groups
+        out = torch.empty((b * n, self.dim), dtype=F32, device=indices.device)
+        idx = indices.to(torch.int64).reshape(g, b * n, q).contiguous()
+        consts = self._consts(indices.device)
+        for gi in range(g):
+            ops.fsq_decode(idx[gi], self.kernel_weights(self.group_params(gi)), consts, len(self.levels), self.num_quantizers, out[:, gi * dg:(gi + 1) * dg])
+        return out.view(b, n, self.dim)
+
+
 # ---------------------------------------------------------------------------------------------- LocalTransformer (soundstream.py:397-440)
 
 _NO_ATTN_BWD = ('training-mode LocalTransformer backward exists for attn_dim_head 32 and 64 with attn_window_size <= 256 (dim_head 64: <= 160) only; got '
@@ -606,11 +704,20 @@ class SoundStream(nn.Module):
                  complex_stft_discr_kwargs: dict = {}, with_mel_loss=False, multi_spectral_window_powers_of_two=tuple(range(6, 12)),
                  multi_spectral_n_ffts=512, multi_spectral_n_mels=64, with_grad_penalty=False, with_film=False, **kwargs):
         super().__init__()
-        if use_lookup_free_quantizer or use_finite_scalar_quantizer or finite_scalar_quantizer_levels is not None:
-            raise NotImplementedError('LFQ / FSQ quantizers are out of scope (SURVEY.md §2)')
+        assert not (use_lookup_free_quantizer and use_finite_scalar_quantizer)                       # soundstream.py:555
+        if use_lookup_free_quantizer:
+            raise NotImplementedError('the lookup-free quantizer (LFQ, use_lookup_free_quantizer=True) is out of scope (SURVEY.md §2)')
         if use_gate_loop_layers or rq_stochastic_sample_codes:
             raise NotImplementedError('gate-loop layers / stochastic code sampling are not implemented (reference defaults False)')
-        assert codebook_size is not None, '`codebook_size` must be set'
+        self.use_lookup_free_quantizer = False
+        self.use_finite_scalar_quantizer = bool(use_finite_scalar_quantizer)
+        if use_finite_scalar_quantizer:                                                              # soundstream.py:576
+            assert codebook_size is None and finite_scalar_quantizer_levels is not None, \
+                'if use_finite_scalar_quantizer is set to True, `finite_scalar_quantizer_levels` must be set (and not `codebook_size`). the effective ' \
+                'codebook size is the cumulative product of all the FSQ levels'
+        else:                                                                                        # soundstream.py:591
+            assert codebook_size is not None and finite_scalar_quantizer_levels is None, \
+                'if use_finite_scalar_quantizer is set to False, `codebook_size` must be set (and not `finite_scalar_quantizer_levels`)'
         self.target_sample_hz = target_sample_hz
         self.single_channel = input_channels == 1
         self.strides = strides
@@ -637,12 +744,21 @@ class SoundStream(nn.Module):
         self.num_quantizers = rq_num_quantizers
         self.codebook_dim = codebook_dim
         self.rq_groups = rq_groups
-        self.codebook_size = codebook_size
-        self.rq = GroupedResidualVQ(dim=codebook_dim, num_quantizers=rq_num_quantizers, codebook_size=codebook_size, groups=rq_groups, decay=rq_ema_decay,
-                                    commitment_weight=rq_commitment_weight, quantize_dropout=True,
-                                    quantize_dropout_cutoff_index=kwargs.get('quantize_dropout_cutoff_index', 1),
-                                    quantize_dropout_multiple_of=rq_quantize_dropout_multiple_of, rotation_trick=rq_rotation_trick, kmeans_iters=10,
-                                    threshold_ema_dead_code=2)                                           # soundstream.py:592-607 (rq_kwargs: ignored, like before)
+        if self.use_finite_scalar_quantizer:                     # soundstream.py:578-588; of rq_kwargs the one key this quantizer takes, others by name
+            unknown = sorted(set(rq_kwargs) - {'quantize_dropout_multiple_of'})
+            if unknown:
+                raise TypeError(f'GroupedResidualFSQ got an unexpected keyword argument {unknown[0]!r} (rq_kwargs: only '
+                                '`quantize_dropout_multiple_of` is implemented for the finite scalar quantizer)')
+            self.rq = GroupedResidualFSQ(dim=codebook_dim, levels=finite_scalar_quantizer_levels, num_quantizers=rq_num_quantizers, groups=rq_groups,
+                                         quantize_dropout=True, quantize_dropout_cutoff_index=kwargs.get('quantize_dropout_cutoff_index', 1), **rq_kwargs)
+            self.codebook_size = self.rq.codebook_size
+        else:
+            self.codebook_size = codebook_size
+            self.rq = GroupedResidualVQ(dim=codebook_dim, num_quantizers=rq_num_quantizers, codebook_size=codebook_size, groups=rq_groups,
+                                        decay=rq_ema_decay, commitment_weight=rq_commitment_weight, quantize_dropout=True,
+                                        quantize_dropout_cutoff_index=kwargs.get('quantize_dropout_cutoff_index', 1),
+                                        quantize_dropout_multiple_of=rq_quantize_dropout_multiple_of, rotation_trick=rq_rotation_trick, kmeans_iters=10,
+                                        threshold_ema_dead_code=2)                                       # soundstream.py:592-607 (rq_kwargs: ignored, like before)
         # the training losses (soundstream.py:629-679) are opt-in: without `with_discriminators=True` nothing below is registered and the loss
         # branches of forward raise, like before
         self.with_discriminators = bool(with_discriminators)
@@ -769,7 +885,11 @@ class SoundStream(nn.Module):
             feats = self.encode(x)
             if denoise_input is not None:                        # soundstream.py:835-837: after encoder_attn, before the quantizer
                 feats = self.encoder_film(feats, denoise_input)
-            quantized, indices, commit_loss = self.rq(feats)
+            if not self.use_finite_scalar_quantizer:
+                quantized, indices, commit_loss = self.rq(feats)
+            else:                                                # soundstream.py:841-845: the finite scalar quantizer has no auxiliary loss
+                quantized, indices = self.rq(feats)
+                commit_loss = torch.zeros((), dtype=F32, device=feats.device)
             if return_codes_only:
                 return indices                                       # (g, b, n, q), soundstream.py:847-848
             b, n = indices.shape[1], indices.shape[2]

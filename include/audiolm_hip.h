@@ -705,6 +705,32 @@ int alm_film_bwd_ws_floats(int rows, int C);
 int alm_film_bwd(const float* g, const float* x, const float* W, const float* b, float* dx, float* dW, float* db, float* ws, long long ws_floats, int rows,
                  int C, float cond0, float cond1, void* stream);
 
+/* ---- residual finite scalar quantization (csrc/fsq.hip; FSQ, arXiv 2309.15505 Appendix A, in the residual form of vector-quantize-pytorch's
+ * GroupedResidualFSQ, restated in tests/fsq_restated.py).  fp32, no float atomics: every output is bitwise reproducible.  One call serves one group:
+ * x / out / g / dx are the group's dim_g columns of row-major matrices with leading dimensions ldx / ldo / ldg / ldd; W_in [d][dim_g], b_in [d],
+ * W_out [dim_g][d], b_out [dim_g] are the nn.Linear tensors as they are, or ALL NULL in the identity case, which needs dim_g == d.
+ * Limits: d <= 8 levels, dim_g <= 1024, Q <= 32 layers, else ALM_ERR_UNSUPPORTED.
+ *   consts : alm_fsq_consts_floats(Q) = 56 + 16 Q floats computed by the caller in double and rounded once to fp32: rows of 8 (entry j < d used)
+ *            half_l, offset, shift, 1 / half_w, half_w, basis, levels, then scale [Q][8] and 1 / scale [Q][8].  The kernels call no atanh / pow.
+ *   alm_fsq_fwd    : z = W_in x + b_in; for q <= k: c_q = rint(tanh(r_q / scale_q + shift) half_l - offset), idx[.][q] = sum_j (c_q[j] + half_w[j])
+ *                    basis[j], r_{q+1} = r_q - c_q / half_w scale_q; idx int64 [M][ldi] (Q columns, -1 past k); out = W_out zsum + b_out; z [M][d]
+ *                    (DOUBLE) is written when not NULL (the backward's input).  x is read once, out written once.  z and the chain are carried
+ *                    in double (scale_q by repeated division): layer q amplifies an error of z by (L - 1)^q, which in fp32 would leave the deep
+ *                    layers' codes to rounding noise; so the indices are those of float64 arithmetic on the same fp32 inputs.
+ *   alm_fsq_decode : idx [M][ldi] (ncols <= Q columns, negative = no code) -> out = W_out (sum_q ((idx_q / basis) % levels - half_w) / half_w scale_q) + b_out
+ *   alm_fsq_bwd    : g_z = W_out^T g; dz = g_z sum_{q <= k} (half_l / half_w) (1 - tanh(..)^2) with the chain recomputed from z; dx = W_in^T dz;
+ *                    dW_in = dz^T x, db_in = sum dz, dW_out = g^T zsum, db_out = sum g as per-row-chunk partials in ws (alm_fsq_bwd_ws_floats floats,
+ *                    owned by the caller; 0 in the identity case), summed in chunk order.  Identity: dx only (z and the gradient pointers unused). */
+int alm_fsq_consts_floats(int Q);
+int alm_fsq_fwd(const float* x, long long ldx, const float* W_in, const float* b_in, const float* W_out, const float* b_out, const float* consts,
+                long long* idx, long long ldi, float* out, long long ldo, double* z, int M, int dim_g, int d, int Q, int k, void* stream);
+int alm_fsq_decode(const long long* idx, long long ldi, const float* W_out, const float* b_out, const float* consts, float* out, long long ldo, int M,
+                   int dim_g, int d, int Q, int ncols, void* stream);
+int alm_fsq_bwd_ws_floats(int M, int dim_g, int d);
+int alm_fsq_bwd(const float* g, long long ldg, const float* x, long long ldx, const double* z, const float* W_in, const float* W_out, const float* consts,
+                float* dx, long long ldd, float* dW_in, float* db_in, float* dW_out, float* db_out, float* ws, long long ws_floats, int M, int dim_g,
+                int d, int Q, int k, void* stream);
+
 /* ---- launch lists (round 6): a recorded sequence of the launches above re-issued by ONE host call ---------------------------------------------
  * The depth loop of audiolm_pytorch.py:528-547 (Transformer.forward) and its backward are ~190 launches per training step whose ORDER and scalar arguments
  * depend only on the model configuration and the batch shape; only buffer addresses change between steps.  The host records the sequence once per shape

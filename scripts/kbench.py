@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty] [se_film]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty] [se_film] [fsq]"""
 import os
 import sys
 import time
@@ -1057,6 +1057,75 @@ def bench_se_film():
     w, b = torch.randn(2 * C, 2, device=dev), torch.randn(2 * C, device=dev)
     t_f, t_b = median([lambda: ops.film_fwd(x, w, b, 1., 0.), lambda: ops.film_bwd(gy, x, w, b, 1., 0.)])
     print(f'film [{rows} x {C}]: fwd {t_f * 1e3:.1f} us   bwd (2 launches) {t_b * 1e3:.1f} us', flush=True)
+
+
+def bench_fsq():
+    """Residual FSQ (csrc/fsq.hip) at 8 x 30 s of 16 kHz audio / 320 = 12 000 tokens, dim 512, levels [8, 5, 5, 5], Q = 8, all layers active:
+    alm_fsq_fwd and alm_fsq_bwd (two launches) beside the same arithmetic written in ATen ops (forward: addmm, the Q-layer chain, addmm; backward:
+    torch autograd of that forward with straight-through rounding), same process, interleaved rounds, medians, one event pair per call.  The rate is
+    on the bytes the op must move (forward: x in, out out = 2 M dim 4 B; backward: g and x in, dx out = 3 M dim 4 B) and is set against the 8 TB/s
+    HBM peak; at this size every operand also fits the 256 MB last-level cache, so the rate is not an HBM measurement."""
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def median(fns, rounds=31, warm=5):
+        for _ in range(warm):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(rounds):
+            for t, fn in zip(ts, fns):
+                t.append(once(fn))
+        return [(sorted(t)[len(t) // 2], sorted(t)[0], sorted(t)[-1]) for t in ts]
+
+    torch.manual_seed(0)
+    M, dim, levels, Q = 12000, 512, (8, 5, 5, 5), 8
+    d, k = len(levels), Q - 1
+    x, g = torch.randn(M, dim, device=dev), torch.randn(M, dim, device=dev)
+    weights = (torch.randn(d, dim, device=dev) * (1.5 / dim ** 0.5), torch.randn(d, device=dev) * 0.1, torch.randn(dim, d, device=dev) * 0.5,
+               torch.randn(dim, device=dev) * 0.1)
+    table = ops.fsq_constants(levels, Q)
+    consts = table.to(dev)
+    head = table[:56].reshape(7, 8)[:, :d].to(dev)
+    half_l, offset, shift, _, half_w, basis, _ = head
+    scale = table[56:56 + 8 * Q].reshape(Q, 8)[:, :d].to(dev)
+    out, dx = torch.empty_like(x), torch.empty_like(x)
+    idx = torch.empty(M, Q, dtype=torch.int64, device=dev)
+    z = ops.fsq_fwd(x, weights, consts, d, Q, k, idx, out, save_z=True)
+
+    def aten_fwd(x, w_in, b_in, w_out, b_out):
+        r = torch.addmm(b_in, x, w_in.t())
+        zsum, inds = 0., []
+        for q in range(Q):
+            b = torch.tanh(r / scale[q] + shift) * half_l - offset
+            code = b + (torch.round(b) - b).detach()
+            inds.append(((code.detach() + half_w) * basis).sum(-1).long())
+            quant = code / half_w * scale[q]
+            r, zsum = r - quant.detach(), zsum + quant
+        return torch.addmm(b_out, zsum, w_out.t()), torch.stack(inds, dim=-1)
+
+    leaves = [t.detach().clone().requires_grad_() for t in (x, *weights)]
+    a_out, a_idx = aten_fwd(*leaves)
+
+    def aten_fwd_nograd():
+        with torch.no_grad():
+            return aten_fwd(x, *weights)
+
+    print(f'fsq [{M} x {dim}], levels {list(levels)}, Q {Q}: indices equal to the ATen chain on {float((a_idx == idx).all(dim=-1).float().mean()):.4%} of '
+          f'the tokens, out rel-max {relerr(out, a_out.detach()):.2e}', flush=True)
+    fns = [lambda: ops.fsq_fwd(x, weights, consts, d, Q, k, idx, out, save_z=True), aten_fwd_nograd,
+           lambda: ops.fsq_bwd(g, x, z, weights, consts, d, Q, k, dx), lambda: torch.autograd.grad(a_out, leaves, g, retain_graph=True)]
+    mb = M * dim * 4 / 1e6
+    for (name, nbytes), (med, lo, hi) in zip((('alm_fsq_fwd', 2 * mb), ('ATen fwd (no grad)', 2 * mb), ('alm_fsq_bwd (2 launches)', 3 * mb),
+                                              ('ATen autograd bwd', 3 * mb)), median(fns)):
+        print(f'  {name:26s} {med * 1e3:8.1f} us (min {lo * 1e3:.1f}, max {hi * 1e3:.1f})   {nbytes / med:7.0f} GB/s on the minimum traffic = '
+              f'{nbytes / med / 8000:.1%} of the 8 TB/s HBM peak', flush=True)
 
 
 if __name__ == '__main__':
