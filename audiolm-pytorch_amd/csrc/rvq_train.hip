@@ -25,7 +25,15 @@
 
 namespace {
 
-constexpr int ST_TILE = 256;             // rows per histogram / scatter tile (= threads per workgroup)
+// The pragma reaches only operations written in THIS file.  The HIP headers' __fmul_rn / __fadd_rn / __fsub_rn are a plain `*`, `+`, `-` compiled under
+// the header's own contraction mode (hipcc's default, fast): once inlined their results still carry the `contract` flag, and the backend fused them
+// into fmas of its choosing, differently in every kernel (u + qh became fma(r, 1 / |r|, qh): not 0 for r = -2 q, and rvq_expire's bits were not
+// rvq_train_quantize's at 4 and more columns per lane; caught by tests/test_gpu_rvq_train_kernels.py).  Hence the single roundings are spelled here.
+__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
+__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
+__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
+
+constexpr int ST_TILE = 256;            // rows per histogram / scatter tile (= threads per workgroup)
 constexpr int ST_CH = 64;                // rows per chunk of a code's row list
 constexpr int ST_CMAX = 8192;            // codes at most (LDS histogram: 32 KB)
 
@@ -172,7 +180,7 @@ template <int K>
 __device__ __forceinline__ void rvq_row_y(const float (&r)[K], const float (&q)[K], int rotation, float (&y)[K], RvqRow<K>& s) {
     if (!rotation) {
 #pragma unroll
-        for (int k = 0; k < K; ++k) y[k] = __fadd_rn(r[k], __fsub_rn(q[k], r[k]));
+        for (int k = 0; k < K; ++k) y[k] = add_rn(r[k], sub_rn(q[k], r[k]));
         return;
     }
     const float rn = __fsqrt_rn(row_dot<K>(r, r)), qn = __fsqrt_rn(row_dot<K>(q, q));
@@ -180,17 +188,17 @@ __device__ __forceinline__ void rvq_row_y(const float (&r)[K], const float (&q)[
     float t[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        s.u[k] = __fmul_rn(r[k], inv_r);
-        s.qh[k] = __fmul_rn(q[k], inv_q);
-        t[k] = __fadd_rn(s.u[k], s.qh[k]);
+        s.u[k] = mul_rn(r[k], inv_r);
+        s.qh[k] = mul_rn(q[k], inv_q);
+        t[k] = add_rn(s.u[k], s.qh[k]);
     }
     const float inv_t = __fdiv_rn(1.f, fmaxf(__fsqrt_rn(row_dot<K>(t, t)), 1e-12f));
 #pragma unroll
-    for (int k = 0; k < K; ++k) s.w[k] = __fmul_rn(t[k], inv_t);
-    const float rw2 = __fmul_rn(2.f, row_dot<K>(r, s.w)), ru2 = __fmul_rn(2.f, row_dot<K>(r, s.u));
-    s.lam = __fmul_rn(qn, inv_r);
+    for (int k = 0; k < K; ++k) s.w[k] = mul_rn(t[k], inv_t);
+    const float rw2 = mul_rn(2.f, row_dot<K>(r, s.w)), ru2 = mul_rn(2.f, row_dot<K>(r, s.u));
+    s.lam = mul_rn(qn, inv_r);
 #pragma unroll
-    for (int k = 0; k < K; ++k) y[k] = __fmul_rn(s.lam, __fmaf_rn(ru2, s.qh[k], __fmaf_rn(-rw2, s.w[k], r[k])));
+    for (int k = 0; k < K; ++k) y[k] = mul_rn(s.lam, __fmaf_rn(ru2, s.qh[k], __fmaf_rn(-rw2, s.w[k], r[k])));
 }
 
 template <int K>
@@ -221,21 +229,21 @@ __global__ __launch_bounds__(256) void rvq_train_quantize_kernel(float* __restri
         row_load<K>(r, resid + row * ldr, lane, d);
         row_load<K>(q, E + c * d, lane, d);
 #pragma unroll
-        for (int k = 0; k < K; ++k) df[k] = __fsub_rn(q[k], r[k]);
-        lsum = __fadd_rn(lsum, row_dot<K>(df, df));
+        for (int k = 0; k < K; ++k) df[k] = sub_rn(q[k], r[k]);
+        lsum = add_rn(lsum, row_dot<K>(df, df));
         rvq_row_y<K>(r, q, rotation, y, s);
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int e = lane + 64 * k;
             if (e < d) {
-                resid[row * ldr + e] = __fsub_rn(r[k], y[k]);
-                out[row * ldo + e] = __fadd_rn(out[row * ldo + e], y[k]);
+                resid[row * ldr + e] = sub_rn(r[k], y[k]);
+                out[row * ldo + e] = add_rn(out[row * ldo + e], y[k]);
             }
         }
     }
     if (lane == 0) sh_loss[wave] = lsum;
     __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = __fadd_rn(__fadd_rn(__fadd_rn(sh_loss[0], sh_loss[1]), sh_loss[2]), sh_loss[3]);
+    if (threadIdx.x == 0) part[blockIdx.x] = add_rn(add_rn(add_rn(sh_loss[0], sh_loss[1]), sh_loss[2]), sh_loss[3]);
 }
 
 // fixed-order sum of n floats by one workgroup: thread t adds elements t, t + 256, ... in order, then a fixed LDS tree.  (every thread returns the total)
@@ -243,7 +251,7 @@ __device__ __forceinline__ float block_sum_fixed(float v, float* sh) {
     sh[threadIdx.x] = v;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] = __fadd_rn(sh[threadIdx.x], sh[threadIdx.x + o]);
+        if ((int)threadIdx.x < o) sh[threadIdx.x] = add_rn(sh[threadIdx.x], sh[threadIdx.x + o]);
         __syncthreads();
     }
     const float total = sh[0];
@@ -254,9 +262,9 @@ __device__ __forceinline__ float block_sum_fixed(float v, float* sh) {
 __global__ __launch_bounds__(256) void rvq_loss_finish_kernel(const float* __restrict__ part, int n, float scale, float* __restrict__ loss) {
     __shared__ float sh[256];
     float acc = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) acc = __fadd_rn(acc, part[i]);
+    for (int i = threadIdx.x; i < n; i += 256) acc = add_rn(acc, part[i]);
     const float total = block_sum_fixed(acc, sh);
-    if (threadIdx.x == 0) loss[0] = __fmul_rn(total, scale);
+    if (threadIdx.x == 0) loss[0] = mul_rn(total, scale);
 }
 
 // one workgroup: cluster_size = cluster_size * decay + n * (1 - decay), its sum over the codes in a fixed order, and the ascending list of the
@@ -274,9 +282,9 @@ __global__ __launch_bounds__(256) void rvq_ema_size_kernel(float* __restrict__ c
         const int c = c0 + threadIdx.x;
         bool is_dead = false;
         if (c < C) {
-            const float v = __fmaf_rn(cluster_size[c], decay, __fmul_rn(n[c], om));
+            const float v = __fmaf_rn(cluster_size[c], decay, mul_rn(n[c], om));
             cluster_size[c] = v;
-            acc = __fadd_rn(acc, v);
+            acc = add_rn(acc, v);
             is_dead = threshold > 0.f && v < threshold;
         }
         const unsigned long long bal = __ballot(is_dead);
@@ -302,9 +310,9 @@ __global__ __launch_bounds__(256) void rvq_ema_embed_kernel(const float* __restr
     const int c = blockIdx.x, col = blockIdx.y * 256 + threadIdx.x;
     if (c >= C || col >= d) return;
     const float tot = total[0];
-    const float smoothed = __fmul_rn(__fdiv_rn(__fadd_rn(cluster_size[c], eps), __fmaf_rn((float)C, eps, tot)), tot);
+    const float smoothed = mul_rn(__fdiv_rn(add_rn(cluster_size[c], eps), __fmaf_rn((float)C, eps, tot)), tot);
     const long long o = (long long)c * d + col;
-    const float ea = __fmaf_rn(embed_avg[o], decay, __fmul_rn(s[o], 1.f - decay));
+    const float ea = __fmaf_rn(embed_avg[o], decay, mul_rn(s[o], 1.f - decay));
     embed_avg[o] = ea;
     embed[o] = __fdiv_rn(ea, smoothed);
 }
@@ -330,14 +338,14 @@ __global__ __launch_bounds__(64) void rvq_expire_kernel(const int* __restrict__ 
         row_load<K>(e, E + ((long long)l * C + c) * d, lane, d);
         rvq_row_y<K>(r, e, rotation, y, s);
 #pragma unroll
-        for (int k = 0; k < K; ++k) r[k] = __fsub_rn(r[k], y[k]);
+        for (int k = 0; k < K; ++k) r[k] = sub_rn(r[k], y[k]);
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int e = lane + 64 * k;
         if (e < d) {
             embed[(long long)code * d + e] = r[k];
-            embed_avg[(long long)code * d + e] = __fmul_rn(r[k], threshold);
+            embed_avg[(long long)code * d + e] = mul_rn(r[k], threshold);
         }
     }
     if (lane == 0) cluster_size[code] = threshold;
@@ -355,7 +363,7 @@ __global__ __launch_bounds__(256) void rvq_kmeans_kernel(float* __restrict__ mea
     means[o] = m;
     if (embed != nullptr) {
         embed[o] = m;
-        embed_avg[o] = __fmul_rn(m, bins);
+        embed_avg[o] = mul_rn(m, bins);
         if (col == 0) cluster_size[c] = bins;
     }
 }
@@ -388,17 +396,17 @@ __global__ __launch_bounds__(256) void rvq_train_bwd_kernel(const float* __restr
         rvq_row_y<K>(r, e, rotation, y, s);
         const float cf = coef != nullptr ? coef[l] : 0.f;
         if (rotation) {
-            const float wg2 = __fmul_rn(2.f, row_dot<K>(s.w, g)), qg2 = __fmul_rn(2.f, row_dot<K>(s.qh, g));
+            const float wg2 = mul_rn(2.f, row_dot<K>(s.w, g)), qg2 = mul_rn(2.f, row_dot<K>(s.qh, g));
 #pragma unroll
-            for (int k = 0; k < K; ++k) acc[k] = __fadd_rn(acc[k], __fmul_rn(s.lam, __fmaf_rn(qg2, s.u[k], __fmaf_rn(-wg2, s.w[k], g[k]))));
+            for (int k = 0; k < K; ++k) acc[k] = add_rn(acc[k], mul_rn(s.lam, __fmaf_rn(qg2, s.u[k], __fmaf_rn(-wg2, s.w[k], g[k]))));
         } else {
 #pragma unroll
-            for (int k = 0; k < K; ++k) acc[k] = __fadd_rn(acc[k], g[k]);
+            for (int k = 0; k < K; ++k) acc[k] = add_rn(acc[k], g[k]);
         }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            acc[k] = __fmaf_rn(cf, __fsub_rn(r[k], e[k]), acc[k]);
-            r[k] = __fsub_rn(r[k], y[k]);
+            acc[k] = __fmaf_rn(cf, sub_rn(r[k], e[k]), acc[k]);
+            r[k] = sub_rn(r[k], y[k]);
         }
     }
 #pragma unroll

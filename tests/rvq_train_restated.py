@@ -193,3 +193,80 @@ class TrainRVQ:
         else:
             outs = [self._group_eval(c, g) for g, c in enumerate(chunks)]
         return torch.cat([o[0] for o in outs], dim=-1), torch.stack([o[1] for o in outs]), torch.stack([o[2] for o in outs])
+
+
+# ---- per-kernel references of csrc/rvq_train.hip (tests/test_gpu_rvq_train_kernels.py).  Indices are INPUTS here (-1 or >= C: the row takes no part);
+# each function restates one `ops.rvq_*` call with the arithmetic of TrainRVQ above.  tests/test_rvq_train_host.py composes them into one training
+# step and finds TrainRVQ.forward + autograd again, so the GPU tests rest on references that are themselves checked without a GPU.
+
+def _taking_part(idx, C):
+    return (idx >= 0) & (idx < C)
+
+
+def layer_y(r, quant, rotation):
+    return rotate_to(r, quant) if rotation else r + (quant - r).detach()
+
+
+def code_stats_ref(r, idx, C):
+    """ops.rvq_code_stats: n [C] rows per code, s [C, d] their sums (TrainRVQ._stats over the rows that take part)"""
+    keep = _taking_part(idx, C)
+    n = torch.zeros(C, dtype=r.dtype).index_add_(0, idx[keep], torch.ones(int(keep.sum()), dtype=r.dtype))
+    s = torch.zeros(C, r.shape[1], dtype=r.dtype).index_add_(0, idx[keep], r[keep])
+    return n, s
+
+
+def quantize_ref(resid, idx, E, out, loss_scale, rotation):
+    """ops.rvq_train_quantize of one layer -> (resid - y, out + y, loss_scale * sum |E[idx] - resid|^2, y); rows that take no part keep resid and out"""
+    keep = _taking_part(idx, E.shape[0])
+    quant = E[idx.clamp(0, E.shape[0] - 1)]
+    y = torch.where(keep[:, None], layer_y(resid, quant, rotation), torch.zeros_like(resid))
+    loss = loss_scale * (torch.where(keep[:, None], quant.detach() - resid, torch.zeros_like(resid)) ** 2).sum()
+    return resid - y.detach(), out + y, loss, y
+
+
+def layer_residual_ref(x, idx, E, q, rotation):
+    """the input residual of layer q of every row of x [M, d], from idx [M, Q] and the codebooks E [Q, C, d] (a layer with no code is a no-op)"""
+    resid = x.detach()
+    for l in range(q):
+        resid = quantize_ref(resid, idx[:, l], E[l], torch.zeros_like(resid), 0., rotation)[0]
+    return resid
+
+
+def bwd_ref(x, idx, E, g_out, coef, rotation):
+    """ops.rvq_train_bwd: autograd of sum(out * g_out) + sum_l coef_l / 2 |r_l - E_l[idx_l]|^2 over the chain of quantize_ref (g_out, coef: None = absent)"""
+    x = x.detach().clone().requires_grad_()
+    resid, out, total = x, torch.zeros_like(x), x.sum() * 0
+    for l in range(E.shape[0]):
+        resid, out, loss, _ = quantize_ref(resid, idx[:, l], E[l], out, 0.5 if coef is None else 0.5 * coef[l], rotation)
+        if coef is not None:
+            total = total + loss
+    if g_out is not None:
+        total = total + (out * g_out).sum()
+    total.backward()
+    return x.grad
+
+
+def ema_update_ref(cluster_size, embed_avg, n, s, decay, eps, threshold):
+    """ops.rvq_ema_update (TrainRVQ._update before the expiry) -> (cluster_size, embed_avg, embed, the ascending list of the codes below the threshold)"""
+    cs = cluster_size * decay + n * (1 - decay)
+    ea = embed_avg * decay + s * (1 - decay)
+    tot = cs.sum()
+    smoothed = (cs + eps) / (tot + cs.numel() * eps) * tot
+    dead = (cs < threshold).nonzero()[:, 0] if threshold > 0 else torch.zeros(0, dtype=torch.int64)
+    return cs, ea, ea / smoothed[:, None], dead
+
+
+def expire_ref(codes, rows, x, idx, E, q, rotation, threshold, cluster_size, embed_avg, embed):
+    """ops.rvq_expire -> the three buffers after it: each listed (code, row) with 0 <= code < C and 0 <= row < M gets embed = the layer-q residual of
+    that row, cluster_size = threshold, embed_avg = threshold * that residual; any other entry is skipped"""
+    cs, ea, em = cluster_size.clone(), embed_avg.clone(), embed.clone()
+    resid = layer_residual_ref(x, idx, E, q, rotation)
+    for code, row in zip(codes.tolist(), rows.tolist()):
+        if 0 <= code < em.shape[0] and 0 <= row < x.shape[0]:
+            em[code], cs[code], ea[code] = resid[row], float(threshold), resid[row] * float(threshold)
+    return cs, ea, em
+
+
+def kmeans_update_ref(means, n, s):
+    """ops.rvq_kmeans_update: an empty bin keeps its mean, the others become s / max(n, 1)"""
+    return torch.where((n == 0)[:, None], means, s / n.clamp(min=1)[:, None])

@@ -102,10 +102,15 @@ SCENARIOS = {
     'expiry': dict(BASE, dim=16, k=3, expiry=True, seed=10),
     'kmeans': dict(BASE, dim=4, Q=2, C=16, k=1, initted=False, seed=11),
     'zero-row': dict(BASE, dim=16, k=3, zero_row=True, seed=12),
+    # the row kernels beyond one column per lane (K = row_k(d) of csrc/rvq_train.hip) and C > 256 (two passes of the EMA kernel's 256-code loop)
+    'wide-k4': dict(BASE, dim=192, Q=2, C=300, b=2, n=45, seed=13),                                   # d = 192: K = 4
+    'wide-g2-k4': dict(BASE, dim=512, groups=2, Q=2, C=300, b=2, n=45, seed=14),                      # d = 256: K = 4 on strided group views
+    'wide-k16': dict(BASE, dim=1000, Q=2, C=40, b=2, n=45, rotation=False, seed=15),                  # d = 1000: K = 16, ragged
+    'wide-expiry': dict(BASE, dim=130, groups=2, Q=3, C=300, b=3, n=30, k=2, expiry=(3, 290), seed=16),   # d = 65: K = 2; the dead list spans both 256-blocks
 }
 # per scenario the seed offset found on a CPU for which the gap assertion holds (see the module docstring); the k-means one also meets an empty cluster
 SEED_OFFSET = {'g1-rot-drop': 0, 'g1-rot': 7, 'g1-st-drop': 0, 'g1-st': 7, 'g2-rot-drop': 14, 'g2-rot': 9, 'g2-st-drop': 0, 'g2-st': 33, 'three-steps': 6, 'expiry': 2,
-               'zero-row': 16}
+               'zero-row': 16, 'wide-k4': 37, 'wide-g2-k4': 65, 'wide-k16': 0, 'wide-expiry': 22}
 
 
 def scenario_inputs(name):
@@ -116,11 +121,11 @@ def scenario_inputs(name):
     books = [[torch.randn(sc['C'], d, generator=g) * 0.6 ** q for q in range(sc['Q'])] for _ in range(sc['groups'])]
     cs = torch.full((sc['C'],), 6.)
     if sc['expiry']:                                                 # two codes nobody is near, with a cluster size that decays below the threshold of 2
+        far = list(sc['expiry']) if isinstance(sc['expiry'], tuple) else [3, 7]
         for grp in books:
             for E in grp:
-                E[3] *= 100
-                E[7] *= 100
-        cs[3] = cs[7] = 1.
+                E[far] *= 100
+        cs[far] = 1.
     xs = [torch.randn(sc['b'], sc['n'], sc['dim'], generator=g) for _ in range(sc['steps'] + 1)]
     if sc['zero_row']:
         xs[0][1, 5] = 0
@@ -251,6 +256,29 @@ def test_expiry_replaces_the_dead_codes(S):
     compare('expiry', got, ref)
     for l in got['steps'][0]['state'][0]:
         assert l['cluster_size'][0, [3, 7]].tolist() == [2., 2.] and torch.equal(l['embed_avg'][0, [3, 7]], 2 * l['embed'][0, [3, 7]])
+
+
+@pytest.mark.parametrize('name', ['wide-k4', 'wide-g2-k4', 'wide-k16'])
+def test_one_wide_training_step(S, name):
+    """b n = 2 x 45, Q = 2: dim 192 (4 columns per lane) with C = 300 | dim 512 in two groups (4 columns per lane on strided views), C = 300 |
+    dim 1000 (16 columns per lane, ragged), C = 40, straight-through"""
+    got = run_gpu(S, name)
+    compare(name, got, reference(name))
+    same_bits(got, run_gpu(S, name))
+
+
+def test_wide_expiry_spans_both_blocks_of_the_dead_list(S):
+    """dim 130 in two groups (d = 65: 2 columns per lane, one column in the second), Q = 3, C = 300: the dead codes 3 and 290 lie in different 256-code
+    passes of the EMA kernel"""
+    got, ref = run_gpu(S, 'wide-expiry'), reference('wide-expiry')
+    for grp in ref['steps'][0]['state']:
+        for st in grp:
+            assert (st['cluster_size'] == 2).nonzero()[:, 0].tolist() == [3, 290]
+    compare('wide-expiry', got, ref)
+    for grp in got['steps'][0]['state']:
+        for l in grp:
+            assert l['cluster_size'][0, [3, 290]].tolist() == [2., 2.] and torch.equal(l['embed_avg'][0, [3, 290]], 2 * l['embed'][0, [3, 290]])
+    same_bits(got, run_gpu(S, 'wide-expiry'))
 
 
 def test_kmeans_init_on_the_first_batch(S):

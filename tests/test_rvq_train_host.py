@@ -1,9 +1,11 @@
 """Host-side checks of the train-mode residual VQ: the restatement (tests/rvq_train_restated.py) against oracle/rvq_restated.py and against hand
-arithmetic, the dropout-index recipe, the constructor options of the product module, and the C ABI of csrc/rvq_train.hip.  No GPU."""
+arithmetic, the dropout-index recipe, the constructor options of the product module, the C ABI of csrc/rvq_train.hip, and the per-kernel references
+of tests/test_gpu_rvq_train_kernels.py composed into one training step against TrainRVQ.forward + autograd.  No GPU."""
 import os
 import random
 import re
 
+import pytest
 import torch
 
 import rvq_restated
@@ -146,3 +148,44 @@ def test_train_kernels_are_exported_and_declared():
     ch = _lib.query('alm_rvq_code_stats_chunk')
     assert _lib.query('alm_rvq_code_stats_ws_floats', 18000, 512, 1024) == 71 * 1024 + 2 * 1025 + 18000 + (18000 // ch + 1024) * 512
     assert _lib.query('alm_rvq_train_quantize_blocks', 0) == 0
+
+
+@pytest.mark.parametrize('name', ['g2-rot-drop', 'expiry'])
+def test_kernel_references_compose_into_the_training_step(name):
+    """statistics -> quantize per layer -> EMA -> expiry -> backward, each by its per-kernel reference (R.code_stats_ref, quantize_ref, ema_update_ref,
+    expire_ref, bwd_ref) on the indices TrainRVQ chose: the step of TrainRVQ.forward + autograd again, float64, max abs difference <= 1e-12.
+    'g2-rot-drop' has two groups and a dropped layer (its index column is -1: a no-op in every reference); 'expiry' expires two codes per layer."""
+    import test_gpu_rvq_train as T
+    sc, seed, books, cs0, xs, gs = T.scenario_inputs(name)
+    want = T.reference(name)['steps'][0]
+    F64 = torch.float64
+    M, Q, C, d = sc['b'] * sc['n'], sc['Q'], sc['C'], sc['dim'] // sc['groups']
+    active = int((want['idx'][0, 0, 0] >= 0).sum())
+    assert active == sc['k'] + 1
+    cw, decay, eps, thr = 1., 0.95, 1e-5, 2.
+    x, g_out, cs0 = xs[0].double().reshape(M, -1), gs[0].double().reshape(M, -1), cs0.double()
+    expired = 0
+
+    def same(what, a, b):
+        assert a.shape == b.shape and float((a - b).abs().max()) <= 1e-12, (name, what, float((a - b).abs().max()))
+
+    for g in range(sc['groups']):
+        xg, idx, E = x[:, g * d:(g + 1) * d], want['idx'][g].reshape(M, Q), torch.stack(books[g]).double()
+        resid, out, losses, stats = xg, torch.zeros(M, d, dtype=F64), [], []
+        for q in range(Q):
+            stats.append(R.code_stats_ref(resid, idx[:, q], C))
+            resid, out, loss, _ = R.quantize_ref(resid, idx[:, q], E[q], out, cw / (M * d), sc['rotation'])
+            losses.append(loss)
+        same('out', out, want['out'].reshape(M, -1)[:, g * d:(g + 1) * d])
+        same('losses', torch.stack(losses), want['losses'][g])
+        assert all(float(l) == 0 for l in losses[active:]) and all(float(n.sum()) == 0 for n, _ in stats[active:])
+        for q in range(active):
+            cs, ea, em, dead = R.ema_update_ref(cs0, E[q] * cs0[:, None], *stats[q], decay, eps, thr)
+            if dead.numel():
+                expired += dead.numel()
+                cs, ea, em = R.expire_ref(dead, T.fixed_rows(M, dead.numel()), xg, idx, E, q, sc['rotation'], thr, cs, ea, em)
+            st = want['state'][g][q]
+            same(f'cluster_size {q}', cs, st['cluster_size']), same(f'embed_avg {q}', ea, st['embed_avg']), same(f'embed {q}', em, st['embed'])
+        coef = torch.tensor([2 * cw / (M * d)] * Q, dtype=F64)       # d(sum of the losses) / d(loss_q) = 1
+        same('dx', R.bwd_ref(xg, idx, E, g_out[:, g * d:(g + 1) * d], coef, sc['rotation']), want['dx'].reshape(M, -1)[:, g * d:(g + 1) * d])
+    assert expired == (2 * active if sc['expiry'] else 0)
