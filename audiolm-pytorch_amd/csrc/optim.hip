@@ -107,27 +107,38 @@ __global__ __launch_bounds__(256) void adam_kernel(OptBatch tb, const int2* __re
     }
 }
 
-// walks the HOST table in batches of OPT_BATCH tensors; the chunk table is tensor-major (all chunks of tensor 0, then tensor 1, ...), so a batch owns a
-// contiguous chunk range.  launch(batch, first chunk, chunk count) issues one kernel.
+// one pass over the whole HOST table BEFORE the first launch (a refusal leaves every tensor untouched: optimizer.py relies on it): lengths >= 0, the
+// pointers this entry point dereferences non-NULL wherever n > 0 (`update`: p, g, m, v; the sum of squares reads g only), and the chunk table is the one
+// of this tensor table (same total chunk count).
+int check_table(const AlmOptTensor* tensors, int ntensors, int nchunks, bool update) {
+    long long nc = 0;
+    for (int i = 0; i < ntensors; ++i) {
+        const AlmOptTensor& t = tensors[i];
+        if (t.n < 0) return ALM_ERR_BAD_ARG;
+        if (t.n > 0 && (!t.g || (update && (!t.p || !t.m || !t.v)))) return ALM_ERR_BAD_ARG;
+        nc += (t.n + CHUNK - 1) / CHUNK;
+    }
+    return nc == (long long)nchunks ? 0 : ALM_ERR_BAD_ARG;
+}
+
+// walks the HOST table (already accepted by check_table) in batches of OPT_BATCH tensors; the chunk table is tensor-major (all chunks of tensor 0, then
+// tensor 1, ...), so a batch owns a contiguous chunk range.  launch(batch, first chunk, chunk count) issues one kernel.
 template <typename F>
-int for_each_batch(const AlmOptTensor* tensors, int ntensors, int nchunks, F launch) {
+void for_each_batch(const AlmOptTensor* tensors, int ntensors, F launch) {
     int c0 = 0;
     for (int t0 = 0; t0 < ntensors; t0 += OPT_BATCH) {
         OptBatch tb;
         tb.t0 = t0;
         const int nt = ntensors - t0 < OPT_BATCH ? ntensors - t0 : OPT_BATCH;
-        long long nc = 0;
+        int nc = 0;
         for (int i = 0; i < nt; ++i) {
             tb.t[i] = tensors[t0 + i];
-            if (tb.t[i].n < 0) return ALM_ERR_BAD_ARG;
-            nc += (tb.t[i].n + CHUNK - 1) / CHUNK;
+            nc += (int)((tb.t[i].n + CHUNK - 1) / CHUNK);
         }
         for (int i = nt; i < OPT_BATCH; ++i) tb.t[i] = AlmOptTensor{nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0};
-        if (c0 + nc > nchunks) return ALM_ERR_BAD_ARG;             // the chunk table does not belong to this tensor table
-        if (nc > 0) launch(tb, c0, (int)nc);
-        c0 += (int)nc;
+        if (nc > 0) launch(tb, c0, nc);
+        c0 += nc;
     }
-    return c0 == nchunks ? 0 : ALM_ERR_BAD_ARG;
 }
 
 // ---- Adam + the bf16 re-pack of the GEMM weights in one pass (round 4).  The dense weights of the stack are consumed as packed bf16 copies (W and W^T,
@@ -208,12 +219,14 @@ extern "C" int alm_opt_chunk_elems(void) { return CHUNK; }
 // tensors: HOST array of ntensors AlmOptTensor (device pointers inside); chunks: DEVICE int32 pairs (tensor index, chunk index), tensor-major.
 // partial: fp32 [nchunks] (sum of squares of each chunk's gradients; alm_reduce_sum over it gives the squared global norm)
 extern "C" int alm_opt_grad_sumsq(const AlmOptTensor* tensors, int ntensors, const int* chunks, int nchunks, float* partial, void* stream) {
-    if (nchunks <= 0 || ntensors <= 0) return 0;
-    if (!tensors || !chunks || !partial) return ALM_ERR_BAD_ARG;
-    const int rc = for_each_batch(tensors, ntensors, nchunks, [&](const OptBatch& tb, int c0, int nc) {
+    if (ntensors <= 0) return 0;
+    if (!tensors) return ALM_ERR_BAD_ARG;
+    if (const int rc = check_table(tensors, ntensors, nchunks, false)) return rc;
+    if (nchunks == 0) return 0;                                       // (every tensor empty)
+    if (!chunks || !partial) return ALM_ERR_BAD_ARG;
+    for_each_batch(tensors, ntensors, [&](const OptBatch& tb, int c0, int nc) {
         hipLaunchKernelGGL(sumsq_kernel, dim3(nc), dim3(256), 0, (hipStream_t)stream, tb, reinterpret_cast<const int2*>(chunks) + c0, partial + c0);
     });
-    if (rc) return rc;
     ALM_LAUNCH_CHECK();
     return 0;
 }
@@ -221,14 +234,16 @@ extern "C" int alm_opt_grad_sumsq(const AlmOptTensor* tensors, int ntensors, con
 // step: 1-based count of THIS step (bias corrections 1 - beta^step) for tensors whose own AlmOptTensor.step is 0.  sumsq: device scalar for the clip (NULL = no clipping).
 extern "C" int alm_opt_adam_step(const AlmOptTensor* tensors, int ntensors, const int* chunks, int nchunks, float lr, float beta1, float beta2, float eps,
                                  int step, int decoupled_weight_decay, const float* sumsq, float max_norm, void* stream) {
-    if (nchunks <= 0 || ntensors <= 0) return 0;
-    if (!tensors || !chunks || step < 1) return ALM_ERR_BAD_ARG;
+    if (ntensors <= 0) return 0;
+    if (!tensors || step < 1) return ALM_ERR_BAD_ARG;
+    if (const int rc = check_table(tensors, ntensors, nchunks, true)) return rc;
+    if (nchunks == 0) return 0;                                       // (every tensor empty)
+    if (!chunks) return ALM_ERR_BAD_ARG;
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     AdamArgs a{lr, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), max_norm, decoupled_weight_decay, sumsq};
-    const int rc = for_each_batch(tensors, ntensors, nchunks, [&](const OptBatch& tb, int c0, int nc) {
+    for_each_batch(tensors, ntensors, [&](const OptBatch& tb, int c0, int nc) {
         hipLaunchKernelGGL(adam_kernel, dim3(nc), dim3(256), 0, (hipStream_t)stream, tb, reinterpret_cast<const int2*>(chunks) + c0, a);
     });
-    if (rc) return rc;
     ALM_LAUNCH_CHECK();
     return 0;
 }

@@ -365,7 +365,10 @@ int alm_mqa_decode_attn(const void* q, long long ldq, void* cache, long long cac
  * tensors per launch -- no staged host-to-device copy per step (the gradient storage moves every step, so the table cannot live on the device);
  * `chunks`: DEVICE int32 pairs (tensor index, chunk index), tensor-major, one per alm_opt_chunk_elems() elements of each tensor (shape-dependent: cached).  alm_opt_grad_sumsq writes one partial sum of squares per chunk (alm_reduce_sum over it =
  * the squared global gradient norm, kept on the device); alm_opt_adam_step applies coef = min(1, max_norm / (sqrt(*sumsq) + 1e-6)) to the
- * gradients on the fly (sumsq NULL: no clipping), then torch.optim.Adam's update (decoupled_weight_decay 1: AdamW).  All fp32. */
+ * gradients on the fly (sumsq NULL: no clipping), then torch.optim.Adam's update (decoupled_weight_decay 1: AdamW).  All fp32.
+ * Both entry points validate the WHOLE table before the first launch, so ALM_ERR_BAD_ARG means that no tensor has been touched: every n >= 0; where
+ * n > 0 the pointers the entry point reads are non-NULL (alm_opt_adam_step: p, g, m, v; alm_opt_grad_sumsq: g only); nchunks equals the table's total
+ * chunk count, sum of ceil(n / alm_opt_chunk_elems()); alm_opt_adam_step: step >= 1.  An entry with n = 0 may carry NULL pointers. */
 typedef struct AlmOptTensor {
     void* p; const void* g; void* m; void* v;   /* parameter, gradient, exp_avg, exp_avg_sq */
     long long n;                                /* elements */
