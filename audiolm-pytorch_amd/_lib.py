@@ -205,6 +205,11 @@ SIGNATURES = {
     'alm_fsq_decode': [_P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     'alm_fsq_bwd_ws_floats': [_I, _I, _I],
     'alm_fsq_bwd': [_P, _L, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    'alm_lfq_fwd_ws_doubles': [_I, _I, _I],
+    'alm_lfq_fwd': [_P, _L, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P],
+    'alm_lfq_decode': [_P, _L, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    'alm_lfq_bwd_ws_floats': [_I, _I, _I, _I],
+    'alm_lfq_bwd': [_P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P],
     'alm_memset_zero': [_P, _L, _P],
     'alm_list_op_id': [ctypes.c_char_p],
     'alm_list_op_nargs': [_I],

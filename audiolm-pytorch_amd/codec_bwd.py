@@ -7,7 +7,7 @@ The forward of each Function runs the SAME forward kernels as the eval path (the
 fused alm_resunit_causal is bitwise equal, with the skip added by alm_add_f32), so a training-mode output is bitwise the eval-mode output.
 Saved per ResidualUnit: its input x, the intermediate h = ELU(conv_k7(x)) and the pre-residual y = ELU(conv_k1(h)) (DESIGN.md gives the memory).
 The squeeze-excite unit (ResidualUnitSEFn) and the FiLM conditioner (FiLMFn) run on csrc/film_se.hip the same way, the residual finite scalar
-quantizer (FsqFn) on csrc/fsq.hip.
+quantizer (FsqFn) on csrc/fsq.hip and the lookup-free quantizer (LfqFn) on csrc/lfq.hip.
 """
 from __future__ import annotations
 
@@ -239,6 +239,40 @@ class FsqFn(torch.autograd.Function):
                 grads.extend(ops.fsq_bwd(g_out[:, sl], x[:, sl], zs[g], weights, consts, d, Q, k, dx[:, sl]))
             else:
                 ops.fsq_bwd(g_out[:, sl], x[:, sl], None, None, consts, d, Q, k, dx[:, sl])
+        need = ctx.needs_input_grad
+        return (dx if need[0] else None, None, None, *[gr if need[3 + i] else None for i, gr in enumerate(grads)])
+
+
+class LfqFn(torch.autograd.Function):
+    """the grouped residual LFQ in training mode (soundstream.GroupedResidualLFQ.run): x [M, dim] -> (out, indices, losses [g, Q]; the indices carry
+    no gradient, the losses do).  `params`: per group project_in.{weight, bias}, project_out.{weight, bias} (nothing in the identity case).  Saved: x,
+    per group the projected input z [M, d] and the mean code distributions avg [Q, 2^d] (both float64), and the parameters; the chain and the softmax
+    are recomputed in alm_lfq_bwd.  Every active layer is straight-through and the residual update detached: dz = (k + 1) g_z + the loss terms."""
+
+    @staticmethod
+    def forward(ctx, x, mod, k, *params):
+        out, idx, losses, saved = mod.run(x, k, with_losses=True)
+        ctx.mod, ctx.k = mod, k
+        ctx.save_for_backward(x, *[t for pair in saved for t in pair], *params)
+        ctx.mark_non_differentiable(idx)
+        return out, idx, losses
+
+    @staticmethod
+    def backward(ctx, g_out, _, g_losses):
+        mod, k = ctx.mod, ctx.k
+        x, *rest = ctx.saved_tensors
+        saved, params = rest[:2 * mod.groups], rest[2 * mod.groups:]
+        M, dim = x.shape
+        dg, d, Q = dim // mod.groups, mod.codebook_bits, mod.num_quantizers
+        g_out = g_out.to(F32).contiguous()
+        g_losses = g_losses.to(F32).contiguous()
+        dx = torch.empty_like(x)
+        per = len(params) // mod.groups                            # 4, or 0 in the identity case
+        grads = []
+        for g in range(mod.groups):
+            sl = slice(g * dg, (g + 1) * dg)
+            weights = mod.kernel_weights(params[per * g:per * g + per])
+            grads.extend(ops.lfq_bwd(g_out[:, sl], g_losses[g], x[:, sl], saved[2 * g], saved[2 * g + 1], weights, d, Q, k, dx[:, sl], mod.loss_cfg))
         need = ctx.needs_input_grad
         return (dx if need[0] else None, None, None, *[gr if need[3 + i] else None for i, gr in enumerate(grads)])
 

@@ -1560,6 +1560,90 @@ def fsq_bwd(g, x, z, weights, consts, d, Q, k, dx):
     return grads
 
 
+# ---- residual lookup-free quantization (csrc/lfq.hip), fp32, no atomics.  One call serves one group, laid out like the FSQ calls above; d =
+# log2(codebook_size); weights = (W_in [d, dim_g], b_in [d], W_out [dim_g, d], b_out [dim_g]) or None (identity, dim_g == d).  `loss_cfg` =
+# (inv_temperature, entropy_loss_weight, commitment_loss_weight, diversity_gamma)
+LFQ_MAX_CODEBOOK_BITS, LFQ_MAX_DIM, LFQ_MAX_QUANTIZERS = 10, 1024, 32
+LFQ_INV_TEMPERATURE = 100.             # the package's default; not a constructor argument of the reference
+
+
+def _lfq_args(mat, weights, d, Q):
+    _chk(mat, F32)
+    M, dim_g = mat.shape
+    assert mat.stride(1) == 1 and d >= 1 and Q >= 1
+    if weights is None:
+        assert dim_g == d, 'the identity case needs dim_g == log2(codebook_size)'
+        return M, dim_g, (None,) * 4
+    w_in, b_in, w_out, b_out = weights
+    for t in weights:
+        _chk(t, F32)
+        assert t.is_contiguous()
+    assert tuple(w_in.shape) == (d, dim_g) and tuple(b_in.shape) == (d,) and tuple(w_out.shape) == (dim_g, d) and tuple(b_out.shape) == (dim_g,)
+    return M, dim_g, tuple(weights)
+
+
+def lfq_fwd(x, weights, d, Q, k, idx_out, out, loss_cfg=None, ws=None):
+    """x [M, dim_g] view -> idx_out int64 [M, Q] view (-1 past layer k) and out [M, dim_g] view, both written in place.  With loss_cfg (training
+    mode) returns (z float64 [M, d], losses fp32 [Q] (0 past k), avg float64 [Q, 2^d] = the mean code distribution per layer: what lfq_bwd needs),
+    else (None, None, None).  ws: a float64 workspace of at least alm_lfq_fwd_ws_doubles elements (allocated when None)  (alm_lfq_fwd)"""
+    M, dim_g, (w_in, b_in, w_out, b_out) = _lfq_args(x, weights, d, Q)
+    _chk(out, F32), _chk(idx_out, torch.int64)
+    assert tuple(out.shape) == (M, dim_g) and out.stride(1) == 1 and tuple(idx_out.shape) == (M, Q) and idx_out.stride(1) == 1
+    z = losses = avg = None
+    tau = w_e = w_c = gamma = 0.
+    if loss_cfg is not None:
+        tau, w_e, w_c, gamma = (float(v) for v in loss_cfg)
+        n = _lib.query('alm_lfq_fwd_ws_doubles', M, d, Q)
+        if n < 0:
+            raise _lib.AlmError('lfq_fwd: outside the kernel limits or a workspace past 2^31 doubles')
+        if ws is None:
+            ws = _new((n,), dtype=torch.float64, device=x.device)
+        _chk(ws, torch.float64)
+        assert ws.is_contiguous()
+        z = _new((M, d), dtype=torch.float64, device=x.device)
+        losses = _new((Q,), dtype=F32, device=x.device)
+        avg = _new((Q, 1 << d), dtype=torch.float64, device=x.device)
+    _lib.call('alm_lfq_fwd', x.data_ptr(), x.stride(0), _p(w_in), _p(b_in), _p(w_out), _p(b_out), idx_out.data_ptr(), idx_out.stride(0), out.data_ptr(),
+              out.stride(0), _p(z), _p(losses), _p(avg), _p(ws) if loss_cfg is not None else None, ws.numel() if loss_cfg is not None else 0, M, dim_g, d,
+              Q, int(k), tau, w_e, w_c, gamma, _st())
+    return z, losses, avg
+
+
+def lfq_decode(idx, weights, d, Q, out):
+    """idx int64 [M, q <= Q] view (negative = no code) -> out [M, dim_g] view, written in place (alm_lfq_decode)"""
+    M, dim_g, (_, _, w_out, b_out) = _lfq_args(out, weights, d, Q)
+    _chk(idx, torch.int64)
+    assert idx.dim() == 2 and idx.shape[0] == M and 1 <= idx.shape[1] <= Q and idx.stride(1) == 1
+    _lib.call('alm_lfq_decode', idx.data_ptr(), idx.stride(0), _p(w_out), _p(b_out), out.data_ptr(), out.stride(0), M, dim_g, d, Q, idx.shape[1], _st())
+    return out
+
+
+def lfq_bwd(g, g_loss, x, z, avg, weights, d, Q, k, dx, loss_cfg, ws=None):
+    """g = dL/dout [M, dim_g] view, g_loss = dL/dlosses fp32 [Q] or None, x view, (z, avg) from lfq_fwd -> dx view written in place; returns (dW_in,
+    db_in, dW_out, db_out), or () in the identity case.  ws: an fp32 workspace of at least alm_lfq_bwd_ws_floats elements (allocated when None)"""
+    M, dim_g, (w_in, _, w_out, _) = _lfq_args(x, weights, d, Q)
+    _chk(g, F32), _chk(dx, F32), _chk(z, torch.float64)
+    assert tuple(g.shape) == (M, dim_g) and g.stride(1) == 1 and tuple(dx.shape) == (M, dim_g) and dx.stride(1) == 1
+    assert z.is_contiguous() and tuple(z.shape) == (M, d)
+    tau, w_e, w_c, gamma = (float(v) for v in loss_cfg)
+    if g_loss is not None:
+        _chk(g_loss, F32), _chk(avg, torch.float64)
+        assert g_loss.is_contiguous() and tuple(g_loss.shape) == (Q,) and avg.is_contiguous() and tuple(avg.shape) == (Q, 1 << d)
+    n = _lib.query('alm_lfq_bwd_ws_floats', M, dim_g, d, Q)
+    if n < 0:
+        raise _lib.AlmError('lfq_bwd: outside the kernel limits or a workspace past 2^31 floats')
+    if ws is None:
+        ws = _new((n,), dtype=F32, device=x.device)
+    _chk(ws, F32)
+    assert ws.is_contiguous()
+    grads = tuple(_new_like(t) for t in weights) if weights is not None else ()
+    dw_in, db_in, dw_out, db_out = grads if grads else (None,) * 4
+    _lib.call('alm_lfq_bwd', g.data_ptr(), g.stride(0), _p(g_loss), x.data_ptr(), x.stride(0), z.data_ptr(), _p(avg) if g_loss is not None else None,
+              _p(w_in), _p(w_out), dx.data_ptr(), dx.stride(0), _p(dw_in), _p(db_in), _p(dw_out), _p(db_out), ws.data_ptr(), ws.numel(), M, dim_g, d, Q,
+              int(k), tau, w_e, w_c, gamma, _st())
+    return grads
+
+
 # ---- HuBERT feature model (csrc/hubert.hip; conv1d_valid and mha_attn are the shared fp32 kernels of csrc/dense_f32.hip) ----
 def hubert_conv0_stats(wave, w, stride, eps=1e-5):
     """wave fp32 [B, Tin] (unit element stride), w fp32 [C, k] -> stats fp32 [B, C, 2] = (mean, rstd) over time of conv1d(wave, w, stride), the

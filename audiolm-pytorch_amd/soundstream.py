@@ -7,7 +7,8 @@ three wave MultiScaleDiscriminators, hinge / feature / reconstruction terms) are
 csrc/discr.hip), and so are the ComplexSTFTDiscriminator, `stft_discriminator=True` (csrc/stft_discr.hip), and the multi-spectral mel-spectrogram
 reconstruction loss, `with_mel_loss=True` (mel_loss.py, csrc/mel_loss.hip), and the gradient penalty of the discriminator loss, `with_grad_penalty=True`
 (a double backward through the discriminator kernels), and the FiLM conditioners of the denoising variant, `with_film=True` (`is_denoising=`;
-csrc/film_se.hip, which also holds the squeeze-excite gate of `squeeze_excite=True` units); the finite scalar quantizer, `use_finite_scalar_quantizer=True` (GroupedResidualFSQ, csrc/fsq.hip); the LFQ quantizer is out of scope and raises.  In training mode the quantizer takes one
+csrc/film_se.hip, which also holds the squeeze-excite gate of `squeeze_excite=True` units); the finite scalar quantizer, `use_finite_scalar_quantizer=True` (GroupedResidualFSQ, csrc/fsq.hip); the lookup-free quantizer, `use_lookup_free_quantizer=True` together with the opt-in `with_lfq=True`
+(GroupedResidualLFQ, csrc/lfq.hip: entropy and commitment losses in training mode, single process; without `with_lfq=True` it raises).  In training mode the quantizer takes one
 training step per call (csrc/rvq_train.hip: quantize dropout, commitment loss, rotation trick, EMA codebooks with dead-code expiry, k-means
 initialisation; single process only), so `forward(x, return_recons_only=True | return_encoded=True)` is differentiable end to end.  The conv encoder / decoder are
 differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
@@ -30,6 +31,7 @@ The module tree keeps the reference's parameter / buffer NAMES for the parts it 
     decoder.0.conv / decoder.{b}.0.conv (ConvTranspose1d) / decoder.{b}.{1,2,3}.fn.{0,2}.conv / decoder.{last}.conv
     rq.rvqs.{g}.layers.{q}._codebook.{initted, cluster_size, embed_avg, embed (1, C, d)}
     rq.rvqs.{g}.{project_in,project_out}.{weight,bias}    GroupedResidualFSQ (use_finite_scalar_quantizer=True only; nothing in the identity case)
+    rq.rvqs.{g}.{project_in,project_out}.{weight,bias}, rq.rvqs.{g}.layers.{q}.mask (int64 2^(d-1) .. 1)    GroupedResidualLFQ (with_lfq=True only)
 """
 from __future__ import annotations
 
@@ -494,6 +496,113 @@ class GroupedResidualFSQ(nn.Module):
         return out.view(b, n, self.dim)
 
 
+class _LFQLayer(nn.Module):
+    def __init__(self, codebook_bits):
+        super().__init__()
+        self.register_buffer('mask', 2 ** torch.arange(codebook_bits - 1, -1, -1, dtype=torch.int64))
+
+
+class _ResidualLFQ(nn.Module):
+    def __init__(self, dim, codebook_bits, num_quantizers):
+        super().__init__()
+        self.project_in = nn.Linear(dim, codebook_bits) if dim != codebook_bits else nn.Identity()
+        self.project_out = nn.Linear(codebook_bits, dim) if dim != codebook_bits else nn.Identity()
+        self.layers = nn.ModuleList([_LFQLayer(codebook_bits) for _ in range(num_quantizers)])
+
+
+class GroupedResidualLFQ(nn.Module):
+    """Residual lookup-free quantization (arXiv 2310.05737) in the grouped form of vector-quantize-pytorch's GroupedResidualLFQ, as the reference
+    builds it (soundstream.py:563-571).  The arithmetic is RESTATED from the paper and the package's residual form (tests/lfq_restated.py; parity with
+    the installed package is unpinned, like FSQ and LocalMHA): per group a projection to d = log2(codebook_size) dimensions, Q layers of sign
+    quantization of the residual at scale 2^-q, a projection back.  No codebook state; in training mode every active layer carries the entropy loss
+    (per-sample entropy minus diversity_gamma times the entropy of the batch's mean code distribution, over all 2^d codes) and the optional
+    commitment loss: alm_lfq_fwd per group, alm_lfq_decode for `get_output_from_indices`, and with a graph wanted codec_bwd.LfqFn (alm_lfq_bwd).
+    rvqs.{g}.project_in / project_out are nn.Linear, or nn.Identity when dim / groups == d; rvqs.{g}.layers.{q}.mask is the package's per-layer
+    buffer (2^(d-1) .. 1, int64).  Quantize dropout (training mode only) is GroupedResidualVQ.dropout_index."""
+
+    def __init__(self, *, dim, num_quantizers, codebook_size, groups=1, quantize_dropout=True, quantize_dropout_cutoff_index=1,
+                 quantize_dropout_multiple_of=1, entropy_loss_weight=0.1, commitment_loss_weight=0., diversity_gamma=1.):
+        super().__init__()
+        codebook_size = int(codebook_size)
+        assert dim % groups == 0 and num_quantizers >= 1
+        assert codebook_size >= 2 and codebook_size & (codebook_size - 1) == 0, f'codebook_size = {codebook_size} must be a power of two >= 2'
+        assert quantize_dropout_cutoff_index >= 0 and quantize_dropout_multiple_of >= 1
+        d, dg = codebook_size.bit_length() - 1, dim // groups
+        if d > ops.LFQ_MAX_CODEBOOK_BITS:
+            raise NotImplementedError(f'GroupedResidualLFQ: log2(codebook_size) = {d} exceeds the kernels\' limit of {ops.LFQ_MAX_CODEBOOK_BITS}')
+        if dg > ops.LFQ_MAX_DIM:
+            raise NotImplementedError(f'GroupedResidualLFQ: dim / groups = {dg} exceeds the kernels\' limit of {ops.LFQ_MAX_DIM}')
+        if num_quantizers > ops.LFQ_MAX_QUANTIZERS:
+            raise NotImplementedError(f'GroupedResidualLFQ: num_quantizers = {num_quantizers} exceeds the kernels\' limit of {ops.LFQ_MAX_QUANTIZERS}')
+        self.dim, self.codebook_size, self.codebook_bits, self.groups, self.num_quantizers = dim, codebook_size, d, groups, num_quantizers
+        self.quantize_dropout = quantize_dropout and num_quantizers > 1
+        self.quantize_dropout_cutoff_index, self.quantize_dropout_multiple_of = quantize_dropout_cutoff_index, quantize_dropout_multiple_of
+        self.entropy_loss_weight, self.commitment_loss_weight, self.diversity_gamma = float(entropy_loss_weight), float(commitment_loss_weight), float(diversity_gamma)
+        self.inv_temperature = ops.LFQ_INV_TEMPERATURE
+        self.rvqs = nn.ModuleList([_ResidualLFQ(dg, d, num_quantizers) for _ in range(groups)])
+
+    dropout_index = GroupedResidualVQ.dropout_index
+    kernel_weights = staticmethod(GroupedResidualFSQ.kernel_weights)
+
+    @property
+    def loss_cfg(self):
+        return (self.inv_temperature, self.entropy_loss_weight, self.commitment_loss_weight, self.diversity_gamma)
+
+    def group_params(self, g):
+        """[project_in.weight, project_in.bias, project_out.weight, project_out.bias] of group g, or [] in the identity case"""
+        r = self.rvqs[g]
+        return [] if isinstance(r.project_in, nn.Identity) else [r.project_in.weight, r.project_in.bias, r.project_out.weight, r.project_out.bias]
+
+    def run(self, x2, k, with_losses=False):
+        """x2 fp32 [M, dim], k = last active layer -> (out [M, dim], idx int64 [g, M, Q] (-1 past k), losses [g, Q] (zeros without with_losses),
+        per group (z [M, d] float64, avg [Q, 2^d] float64) or None)"""
+        M, dim = x2.shape
+        dg, d, Q = dim // self.groups, self.codebook_bits, self.num_quantizers
+        out = torch.empty((M, dim), dtype=F32, device=x2.device)
+        idx = torch.empty((self.groups, M, Q), dtype=torch.int64, device=x2.device)
+        losses, saved = [], []
+        for g in range(self.groups):
+            weights = self.kernel_weights(self.group_params(g))
+            z, l, avg = ops.lfq_fwd(x2[:, g * dg:(g + 1) * dg], weights, d, Q, k, idx[g], out[:, g * dg:(g + 1) * dg],
+                                    loss_cfg=self.loss_cfg if with_losses else None)
+            losses.append(l)
+            saved.append((z, avg) if with_losses else None)
+        losses = torch.stack(losses) if with_losses else torch.zeros((self.groups, Q), dtype=F32, device=x2.device)
+        return out, idx, losses, saved
+
+    def forward(self, x):
+        """x fp32 (b, n, dim) -> (quantized (b, n, dim), indices (g, b, n, q) int64; -1 on the layers quantize dropout left out, losses (g, q):
+        zeros in eval mode and on the layers left out)"""
+        if not x.is_cuda:
+            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
+        if self.training and torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise NotImplementedError('train-mode GroupedResidualLFQ is single-process: the all-reduce of the mean code distribution (the diversity '
+                                      'term of the entropy loss) is not implemented')
+        b, n, dim = x.shape
+        assert dim == self.dim
+        x2 = x.reshape(b * n, dim).to(F32).contiguous()
+        k = self.dropout_index() if self.training else self.num_quantizers - 1
+        if self.training and codec_bwd.wants_grad(self, x2):
+            out, idx, losses = codec_bwd.LfqFn.apply(x2, self, k, *[p for g in range(self.groups) for p in self.group_params(g)])
+        else:
+            out, idx, losses, _ = self.run(x2.detach(), k, with_losses=self.training)
+        return out.view(b, n, dim), idx.view(self.groups, b, n, self.num_quantizers), losses
+
+    @torch.no_grad()
+    def get_output_from_indices(self, indices):
+        """indices int (g, b, n, q <= Q) (-1 = no code) -> (b, n, dim): per group project_out of the summed codes (alm_lfq_decode)"""
+        g, b, n, q = indices.shape
+        assert g == self.groups and 1 <= q <= self.num_quantizers
+        if not indices.is_cuda:
+            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
+        dg = self.dim // self.groups
+        out = torch.empty((b * n, self.dim), dtype=F32, device=indices.device)
+        idx = indices.to(torch.int64).reshape(g, b * n, q).contiguous()
+        for gi in range(g):
+            ops.lfq_decode(idx[gi], self.kernel_weights(self.group_params(gi)), self.codebook_bits, self.num_quantizers, out[:, gi * dg:(gi + 1) * dg])
+        return out.view(b, n, self.dim)
+
+
 # ---------------------------------------------------------------------------------------------- LocalTransformer (soundstream.py:397-440)
 
 _NO_ATTN_BWD = ('training-mode LocalTransformer backward exists for attn_dim_head 32 and 64 with attn_window_size <= 256 (dim_head 64: <= 160) only; got '
@@ -702,16 +811,20 @@ class SoundStream(nn.Module):
                  attn_xpos_scale_base=None, attn_dynamic_pos_bias=False, use_gate_loop_layers=False, squeeze_excite=False, pad_mode='reflect',
                  stft_discriminator=None, with_discriminators=False, stft_normalized=False, complex_stft_discr_logits_abs=True,
                  complex_stft_discr_kwargs: dict = {}, with_mel_loss=False, multi_spectral_window_powers_of_two=tuple(range(6, 12)),
-                 multi_spectral_n_ffts=512, multi_spectral_n_mels=64, with_grad_penalty=False, with_film=False, **kwargs):
+                 multi_spectral_n_ffts=512, multi_spectral_n_mels=64, with_grad_penalty=False, with_film=False, with_lfq=False, **kwargs):
         super().__init__()
         assert not (use_lookup_free_quantizer and use_finite_scalar_quantizer)                       # soundstream.py:555
-        if use_lookup_free_quantizer:
-            raise NotImplementedError('the lookup-free quantizer (LFQ, use_lookup_free_quantizer=True) is out of scope (SURVEY.md §2)')
+        if use_lookup_free_quantizer and not with_lfq:
+            raise NotImplementedError('the lookup-free quantizer (LFQ, use_lookup_free_quantizer=True) is opt-in in this port: pass with_lfq=True '
+                                      '(GroupedResidualLFQ; its arithmetic is restated from the paper, parity with the installed package is unpinned)')
         if use_gate_loop_layers or rq_stochastic_sample_codes:
             raise NotImplementedError('gate-loop layers / stochastic code sampling are not implemented (reference defaults False)')
-        self.use_lookup_free_quantizer = False
+        self.use_lookup_free_quantizer = bool(use_lookup_free_quantizer)
         self.use_finite_scalar_quantizer = bool(use_finite_scalar_quantizer)
-        if use_finite_scalar_quantizer:                                                              # soundstream.py:576
+        if use_lookup_free_quantizer:                                                                # soundstream.py:561
+            assert codebook_size is not None and finite_scalar_quantizer_levels is None, \
+                'if use_finite_scalar_quantizer is set to False, `codebook_size` must be set (and not `finite_scalar_quantizer_levels`)'
+        elif use_finite_scalar_quantizer:                                                            # soundstream.py:576
             assert codebook_size is None and finite_scalar_quantizer_levels is not None, \
                 'if use_finite_scalar_quantizer is set to True, `finite_scalar_quantizer_levels` must be set (and not `codebook_size`). the effective ' \
                 'codebook size is the cumulative product of all the FSQ levels'
@@ -744,7 +857,16 @@ class SoundStream(nn.Module):
         self.num_quantizers = rq_num_quantizers
         self.codebook_dim = codebook_dim
         self.rq_groups = rq_groups
-        if self.use_finite_scalar_quantizer:                     # soundstream.py:578-588; of rq_kwargs the one key this quantizer takes, others by name
+        if self.use_lookup_free_quantizer:                       # soundstream.py:563-573; of rq_kwargs the keys this quantizer takes, others by name
+            taken = {'quantize_dropout_multiple_of', 'entropy_loss_weight', 'commitment_loss_weight', 'diversity_gamma'}
+            unknown = sorted(set(rq_kwargs) - taken)
+            if unknown:
+                raise TypeError(f'GroupedResidualLFQ got an unexpected keyword argument {unknown[0]!r} (rq_kwargs: only '
+                                f'{", ".join("`" + t + "`" for t in sorted(taken))} are implemented for the lookup-free quantizer)')
+            self.rq = GroupedResidualLFQ(dim=codebook_dim, num_quantizers=rq_num_quantizers, codebook_size=codebook_size, groups=rq_groups,
+                                         quantize_dropout=True, quantize_dropout_cutoff_index=kwargs.get('quantize_dropout_cutoff_index', 1), **rq_kwargs)
+            self.codebook_size = codebook_size
+        elif self.use_finite_scalar_quantizer:                   # soundstream.py:578-588; of rq_kwargs the one key this quantizer takes, others by name
             unknown = sorted(set(rq_kwargs) - {'quantize_dropout_multiple_of'})
             if unknown:
                 raise TypeError(f'GroupedResidualFSQ got an unexpected keyword argument {unknown[0]!r} (rq_kwargs: only '

@@ -734,6 +734,36 @@ int alm_fsq_bwd(const float* g, long long ldg, const float* x, long long ldx, co
                 float* dx, long long ldd, float* dW_in, float* db_in, float* dW_out, float* db_out, float* ws, long long ws_floats, int M, int dim_g,
                 int d, int Q, int k, void* stream);
 
+/* ---- residual lookup-free quantization (csrc/lfq.hip; LFQ, arXiv 2310.05737, in the residual form of vector-quantize-pytorch's GroupedResidualLFQ,
+ * restated in tests/lfq_restated.py).  fp32 tensors, no float atomics: every output is bitwise reproducible.  One call serves one group, laid out
+ * like the FSQ calls above (column views with leading dimensions; W_in [d][dim_g], b_in [d], W_out [dim_g][d], b_out [dim_g], or ALL NULL in the
+ * identity case dim_g == d).  d = log2(codebook_size).  Limits: d <= 10, dim_g <= 1024, Q <= 32, else ALM_ERR_UNSUPPORTED.
+ *   alm_lfq_fwd    : z = W_in x + b_in; for q <= k, s_q = 2^-q: bit_q[j] = r_q[j] > 0, quant_q = +-s_q, idx[.][q] = sum_j bit_q[j] 2^(d-1-j),
+ *                    r_{q+1} = r_q - quant_q; idx int64 [M][ldi] (Q columns, -1 past k); out = W_out (sum_q quant_q) + b_out.  z and the chain are
+ *                    carried in DOUBLE (the logits of layer q multiply an error of z by 2 inv_temperature 2^-q); z [M][d] (double) is written when
+ *                    not NULL.  With losses != NULL (training mode; needs z, avg and ws) also, per layer q <= k, with p_m = softmax_c(2
+ *                    inv_temperature <r_q[m], C_q[c]>) over the 2^d sign patterns C_q[c] = +-s_q and H(t) = -sum_c t_c log max(t_c, 1e-5):
+ *                      losses[q] = entropy_w (mean_m H(p_m) - gamma H(mean_m p_m)) + commit_w mean_{m,j} (r_q - quant_q)^2      (0 for q > k)
+ *                    and avg [Q][2^d] (double) = mean_m p_m (zero rows for q > k), which the backward needs.  The softmax factorises over the bits, so a
+ *                    probability is a product of d per-bit sigmoids, formed in double for all 2^d codes; the sum over the rows goes through
+ *                    per-row-chunk partials in ws (alm_lfq_fwd_ws_doubles doubles, owned by the caller) added in chunk order by a finish launch.
+ *   alm_lfq_decode : idx [M][ldi] (ncols <= Q columns, negative = no code) -> out = W_out (sum_q +-2^-q by the bits of idx_q) + b_out
+ *   alm_lfq_bwd    : g_z = W_out^T g; dz = (k + 1) g_z + sum_{q <= k} g_loss[q] d losses[q] / d r_q (the chain recomputed from z; g_loss [Q] floats
+ *                    on the device, or NULL for none); dx = W_in^T dz; dW_in = dz^T x, db_in = sum dz, dW_out = g^T zsum, db_out = sum g as
+ *                    per-row-chunk partials summed in chunk order.  ws: alm_lfq_bwd_ws_floats floats (the per-layer loss gradients [Q][M][d], then
+ *                    the partials).  Identity: dx only (the parameter pointers NULL); z is still needed. */
+int alm_lfq_fwd_ws_doubles(int M, int d, int Q);
+int alm_lfq_fwd(const float* x, long long ldx, const float* W_in, const float* b_in, const float* W_out, const float* b_out, long long* idx,
+                long long ldi, float* out, long long ldo, double* z, float* losses, double* avg, double* ws, long long ws_doubles, int M, int dim_g,
+                int d, int Q, int k, float inv_temperature, float entropy_w, float commit_w, float gamma, void* stream);
+int alm_lfq_decode(const long long* idx, long long ldi, const float* W_out, const float* b_out, float* out, long long ldo, int M, int dim_g, int d,
+                   int Q, int ncols, void* stream);
+int alm_lfq_bwd_ws_floats(int M, int dim_g, int d, int Q);
+int alm_lfq_bwd(const float* g, long long ldg, const float* g_loss, const float* x, long long ldx, const double* z, const double* avg,
+                const float* W_in, const float* W_out, float* dx, long long ldd, float* dW_in, float* db_in, float* dW_out, float* db_out, float* ws,
+                long long ws_floats, int M, int dim_g, int d, int Q, int k, float inv_temperature, float entropy_w, float commit_w, float gamma,
+                void* stream);
+
 /* ---- launch lists (round 6): a recorded sequence of the launches above re-issued by ONE host call ---------------------------------------------
  * The depth loop of audiolm_pytorch.py:528-547 (Transformer.forward) and its backward are ~190 launches per training step whose ORDER and scalar arguments
  * depend only on the model configuration and the batch shape; only buffer addresses change between steps.  The host records the sequence once per shape

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty] [se_film] [fsq]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty] [se_film] [fsq] [lfq]"""
 import os
 import sys
 import time
@@ -1126,6 +1126,87 @@ def bench_fsq():
                                               ('ATen autograd bwd', 3 * mb)), median(fns)):
         print(f'  {name:26s} {med * 1e3:8.1f} us (min {lo * 1e3:.1f}, max {hi * 1e3:.1f})   {nbytes / med:7.0f} GB/s on the minimum traffic = '
               f'{nbytes / med / 8000:.1%} of the 8 TB/s HBM peak', flush=True)
+
+
+def bench_lfq():
+    """Residual LFQ (csrc/lfq.hip) at 8 x 45 s of 16 kHz audio / 320 = 18 000 tokens, dim 512, 1024 codes (d = 10), Q = 8, all layers active, training
+    mode: alm_lfq_fwd (three launches: projection + chain, the code statistics, the finish) and alm_lfq_bwd (three launches, the loss gradient
+    included) beside (a) the dense torch formulation of tests/lfq_restated.py in fp32 on the same GPU (explicit [1024, 10] codebook, einsum, softmax,
+    clamped log, autograd) and (b) the FSQ kernels at the same M / dim ([8, 5, 5, 5], Q = 8).  Same process, interleaved rounds, medians, one event
+    pair per call.  The LFQ work is arithmetic, not traffic: M Q 2^d = 147 M probabilities per pass, each formed in double."""
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def median(fns, rounds=15, warm=3):
+        for _ in range(warm):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(rounds):
+            for t, fn in zip(ts, fns):
+                t.append(once(fn))
+        return [(sorted(t)[len(t) // 2], sorted(t)[0], sorted(t)[-1]) for t in ts]
+
+    torch.manual_seed(0)
+    M, dim, d, Q = 8 * 2250, 512, 10, 8
+    k, cfg = Q - 1, (ops.LFQ_INV_TEMPERATURE, 0.1, 0.25, 1.)
+    tau, w_e, w_c, gamma = cfg
+    x, g = torch.randn(M, dim, device=dev), torch.randn(M, dim, device=dev)
+    g_loss = torch.randn(Q, device=dev)
+    weights = (torch.randn(d, dim, device=dev) * (1.5 / dim ** 0.5), torch.randn(d, device=dev) * 0.1, torch.randn(dim, d, device=dev) * 0.5,
+               torch.randn(dim, device=dev) * 0.1)
+    out, dx = torch.empty_like(x), torch.empty_like(x)
+    idx = torch.empty(M, Q, dtype=torch.int64, device=dev)
+    ws_f = torch.empty(_lib.query('alm_lfq_fwd_ws_doubles', M, d, Q), dtype=torch.float64, device=dev)
+    ws_b = torch.empty(_lib.query('alm_lfq_bwd_ws_floats', M, dim, d, Q), device=dev)
+    z, losses, avg = ops.lfq_fwd(x, weights, d, Q, k, idx, out, loss_cfg=cfg, ws=ws_f)
+    mask = 2 ** torch.arange(d - 1, -1, -1, device=dev)
+    sigma = ((torch.arange(2 ** d, device=dev)[:, None] & mask) != 0).float() * 2 - 1
+
+    def dense_fwd(x, w_in, b_in, w_out, b_out):
+        r = torch.addmm(b_in, x, w_in.t())
+        zsum, inds, ls = 0., [], []
+        for q in range(Q):
+            s = 2. ** -q
+            hard = torch.where(r > 0, s, -s).detach()
+            inds.append(((r > 0).long() * mask).sum(-1))
+            p = (2 * tau * torch.einsum('md,cd->mc', r, sigma * s)).softmax(dim=-1)
+            avg_p = p.mean(dim=0)
+            ent = (-p * torch.log(p.clamp(min=1e-5))).sum(-1).mean() - gamma * (-avg_p * torch.log(avg_p.clamp(min=1e-5))).sum()
+            ls.append(w_e * ent + w_c * torch.nn.functional.mse_loss(r, hard))
+            zsum, r = zsum + r + (hard - r).detach(), r - hard
+        return torch.addmm(b_out, zsum, w_out.t()), torch.stack(inds, dim=-1), torch.stack(ls)
+
+    leaves = [t.detach().clone().requires_grad_() for t in (x, *weights)]
+    a_out, a_idx, a_losses = dense_fwd(*leaves)
+
+    def dense_fwd_nograd():
+        with torch.no_grad():
+            return dense_fwd(x, *weights)
+
+    levels = (8, 5, 5, 5)
+    f_consts = ops.fsq_constants(levels, Q).to(dev)
+    f_w = (torch.randn(4, dim, device=dev) * (1.5 / dim ** 0.5), torch.randn(4, device=dev) * 0.1, torch.randn(dim, 4, device=dev) * 0.5,
+           torch.randn(dim, device=dev) * 0.1)
+    f_z = ops.fsq_fwd(x, f_w, f_consts, 4, Q, k, idx.clone(), torch.empty_like(x), save_z=True)
+    f_idx, f_out = torch.empty_like(idx), torch.empty_like(x)
+    print(f'lfq [{M} x {dim}], {2 ** d} codes, Q {Q}: indices equal to the dense fp32 formulation on {float((a_idx == idx).all(dim=-1).float().mean()):.4%} '
+          f'of the tokens, out rel-max {relerr(out, a_out.detach()):.2e}, losses rel-max {relerr(losses, a_losses.detach()):.2e}', flush=True)
+    fns = [lambda: ops.lfq_fwd(x, weights, d, Q, k, idx, out, loss_cfg=cfg, ws=ws_f), dense_fwd_nograd,
+           lambda: ops.fsq_fwd(x, f_w, f_consts, 4, Q, k, f_idx, f_out, save_z=True),
+           lambda: ops.lfq_bwd(g, g_loss, x, z, avg, weights, d, Q, k, dx, cfg, ws=ws_b),
+           lambda: torch.autograd.grad([a_out, a_losses], leaves, [g, g_loss], retain_graph=True),
+           lambda: ops.fsq_bwd(g, x, f_z, f_w, f_consts, 4, Q, k, dx)]
+    names = ('alm_lfq_fwd (3 launches)', 'dense torch fwd (no grad)', 'alm_fsq_fwd', 'alm_lfq_bwd (3 launches)', 'dense torch autograd bwd',
+             'alm_fsq_bwd (2 launches)')
+    for name, (med, lo, hi) in zip(names, median(fns)):
+        print(f'  {name:28s} {med * 1e3:9.1f} us (min {lo * 1e3:.1f}, max {hi * 1e3:.1f})', flush=True)
 
 
 if __name__ == '__main__':
