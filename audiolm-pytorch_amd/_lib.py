@@ -210,6 +210,13 @@ SIGNATURES = {
     'alm_lfq_decode': [_P, _L, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     'alm_lfq_bwd_ws_floats': [_I, _I, _I, _I],
     'alm_lfq_bwd': [_P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P],
+    'alm_gate_loop_chunk': [],
+    'alm_gate_loop_norm_fwd': [_P, _P, _P, _I, _I, _I, _P],
+    'alm_gate_loop_scan_ws_floats': [_I, _I, _I],
+    'alm_gate_loop_scan_fwd': [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    'alm_gate_loop_scan_bwd': [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
+    'alm_gate_loop_norm_bwd_ws_floats': [_I, _I, _I],
+    'alm_gate_loop_norm_bwd': [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
     'alm_memset_zero': [_P, _L, _P],
     'alm_list_op_id': [ctypes.c_char_p],
     'alm_list_op_nargs': [_I],

@@ -349,6 +349,30 @@ class LocalFeedForwardFn(torch.autograd.Function):
         return dx if need[0] else None, dgamma, dbeta, dw1, dw2, None, None
 
 
+class GateLoopFn(torch.autograd.Function):
+    """the gate-loop block q * h + 2 x (soundstream.Residual.launches).  Saved: x and z = to_qkva(RMSNorm(x)) (4 dim floats per frame, 16 bytes per
+    element of x); RMSNorm(x) and the state h are recomputed in the backward (one launch each: 8 bytes per element less than keeping them)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, weight, block):
+        z, y = block.launches(x)
+        ctx.block = block
+        ctx.save_for_backward(x, z, gamma, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, z, gamma, _ = ctx.saved_tensors
+        layer, need = ctx.block.layer, ctx.needs_input_grad
+        g = g.to(F32).contiguous()
+        gamma = gamma.detach().to(F32).contiguous()
+        dz = ops.gate_loop_scan_bwd(g, z, ops.gate_loop_scan_fwd(z))
+        xn = ops.gate_loop_norm_fwd(x, gamma) if need[2] else x          # only the weight gradient reads xn's values
+        dxn, dw, _ = _lin_bwd(layer._lin, layer.to_qkva[0], dz, xn, True, need[2])
+        dx, dgamma = ops.gate_loop_norm_bwd(dxn, x, gamma, g)
+        return dx if need[0] else None, dgamma if need[1] else None, dw, None
+
+
 def ff_launches(ff, lins, x):
     """(LN(x), u, GEGLU(u), W2 GEGLU(u) + x) of one feed-forward block (ff: the Sequential, lins: its two soundstream._Linear1x1)"""
     xn = ops.layernorm_bct(x, ff[0].weight.detach(), ff[0].bias.detach(), ff[0].eps)

@@ -1644,6 +1644,74 @@ def lfq_bwd(g, g_loss, x, z, avg, weights, d, Q, k, dx, loss_cfg, ws=None):
     return grads
 
 
+# ---- gate-loop layer of SoundStream(use_gate_loop_layers=True) (csrc/gate_loop.hip), exact fp32, no atomics; codec layout [B, C, T]
+
+GATE_LOOP_CHUNK = 4096                 # steps one workgroup scans (alm_gate_loop_chunk): longer rows take the three-launch form
+
+
+def _gl_dims(x):
+    _chk(x, F32)
+    assert x.dim() == 3 and x.is_contiguous()
+    return x.shape
+
+
+def _gl_scan_ws(B, C, T, device):
+    n = _lib.query('alm_gate_loop_scan_ws_floats', B, C, T)
+    if n < 0:
+        raise _lib.AlmError('gate_loop scan: B * C * ceil(T / GATE_LOOP_CHUNK) exceeds the kernels\' limit (2^31 / 3)')
+    return _new((n,), dtype=F32, device=device) if n else None
+
+
+def gate_loop_norm_fwd(x, gamma):
+    """x fp32 [B, C, T], gamma [C] -> x * r * gamma, r = sqrt(C) / max(||x[b, :, t]||, 1e-12): RMSNorm over the channel axis"""
+    B, C, T = _gl_dims(x)
+    _chk(gamma, F32)
+    assert gamma.is_contiguous() and tuple(gamma.shape) == (C,)
+    xn = _new_like(x)
+    _lib.call('alm_gate_loop_norm_fwd', x.data_ptr(), gamma.data_ptr(), xn.data_ptr(), B, C, T, _st())
+    return xn
+
+
+def gate_loop_scan_fwd(z, x=None):
+    """z fp32 [B, 3 C, T] (rows q | kv | a), x [B, C, T] -> q * h + 2 x with h[t] = sigmoid(a[t]) h[t-1] + kv[t], h[0] = kv[0]; x=None -> h itself"""
+    B, C3, T = _gl_dims(z)
+    assert C3 % 3 == 0
+    C = C3 // 3
+    if x is not None:
+        assert tuple(_gl_dims(x)) == (B, C, T)
+    out = _new((B, C, T), dtype=F32, device=z.device)
+    ws = _gl_scan_ws(B, C, T, z.device)
+    _lib.call('alm_gate_loop_scan_fwd', z.data_ptr(), _p(x), out.data_ptr(), _p(ws), 0 if ws is None else ws.numel(), B, C, T, int(x is None), _st())
+    return out
+
+
+def gate_loop_scan_bwd(g, z, h):
+    """g = dL/dout [B, C, T], z [B, 3 C, T], h = gate_loop_scan_fwd(z) -> dz [B, 3 C, T] (dq | dkv | da rows; da is exactly 0 at t = 0); the 2 g of
+    the two skips is left to gate_loop_norm_bwd"""
+    B, C, T = _gl_dims(g)
+    assert tuple(_gl_dims(z)) == (B, 3 * C, T) and tuple(_gl_dims(h)) == (B, C, T)
+    dz = _new_like(z)
+    ws = _gl_scan_ws(B, C, T, z.device)
+    _lib.call('alm_gate_loop_scan_bwd', g.data_ptr(), z.data_ptr(), h.data_ptr(), dz.data_ptr(), _p(ws), 0 if ws is None else ws.numel(), B, C, T, _st())
+    return dz
+
+
+def gate_loop_norm_bwd(dxn, x, gamma, g):
+    """dxn = dL/d(gate_loop_norm_fwd(x, gamma)), g = dL/dout of the block -> (dx [B, C, T] including the 2 g of the two skips, dgamma [C]); dgamma's
+    per-block partials in a workspace of alm_gate_loop_norm_bwd_ws_floats floats, added in block order"""
+    B, C, T = _gl_dims(x)
+    _chk(gamma, F32)
+    assert tuple(_gl_dims(dxn)) == (B, C, T) and tuple(_gl_dims(g)) == (B, C, T) and gamma.is_contiguous() and tuple(gamma.shape) == (C,)
+    n = _lib.query('alm_gate_loop_norm_bwd_ws_floats', B, C, T)
+    if n < 0:
+        raise _lib.AlmError('gate_loop_norm_bwd: the partial-sum workspace exceeds 2^31 floats')
+    ws = _new((n,), dtype=F32, device=x.device)
+    dx, dgamma = _new_like(x), _new_like(gamma)
+    _lib.call('alm_gate_loop_norm_bwd', dxn.data_ptr(), x.data_ptr(), gamma.data_ptr(), g.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), ws.data_ptr(), n,
+              B, C, T, _st())
+    return dx, dgamma
+
+
 # ---- HuBERT feature model (csrc/hubert.hip; conv1d_valid and mha_attn are the shared fp32 kernels of csrc/dense_f32.hip) ----
 def hubert_conv0_stats(wave, w, stride, eps=1e-5):
     """wave fp32 [B, Tin] (unit element stride), w fp32 [C, k] -> stats fp32 [B, C, 2] = (mean, rstd) over time of conv1d(wave, w, stride), the

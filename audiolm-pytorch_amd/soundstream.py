@@ -8,7 +8,9 @@ csrc/discr.hip), and so are the ComplexSTFTDiscriminator, `stft_discriminator=Tr
 reconstruction loss, `with_mel_loss=True` (mel_loss.py, csrc/mel_loss.hip), and the gradient penalty of the discriminator loss, `with_grad_penalty=True`
 (a double backward through the discriminator kernels), and the FiLM conditioners of the denoising variant, `with_film=True` (`is_denoising=`;
 csrc/film_se.hip, which also holds the squeeze-excite gate of `squeeze_excite=True` units); the finite scalar quantizer, `use_finite_scalar_quantizer=True` (GroupedResidualFSQ, csrc/fsq.hip); the lookup-free quantizer, `use_lookup_free_quantizer=True` together with the opt-in `with_lfq=True`
-(GroupedResidualLFQ, csrc/lfq.hip: entropy and commitment losses in training mode, single process; without `with_lfq=True` it raises).  In training mode the quantizer takes one
+(GroupedResidualLFQ, csrc/lfq.hip: entropy and commitment losses in training mode, single process; without `with_lfq=True` it raises); the gate-loop
+layers, `use_gate_loop_layers=True` together with the opt-in `with_gate_loop=True` (one GateLoopBlock after every encoder / decoder block: a linear
+recurrence along time as a parallel scan, csrc/gate_loop.hip; without `with_gate_loop=True` it raises).  In training mode the quantizer takes one
 training step per call (csrc/rvq_train.hip: quantize dropout, commitment loss, rotation trick, EMA codebooks with dead-code expiry, k-means
 initialisation; single process only), so `forward(x, return_recons_only=True | return_encoded=True)` is differentiable end to end.  The conv encoder / decoder are
 differentiable: in training mode, with grad mode on and an input or parameter that requires grad, `encode` / `decode` / `decode_from_codebook_indices`
@@ -24,6 +26,8 @@ The module tree keeps the reference's parameter / buffer NAMES for the parts it 
     encoder.{b}.{r}.fn.{0,2}.conv.{weight,bias}         ResidualUnit r of EncoderBlock b (k7 dilated conv, ELU, k1 conv, ELU, + x)
     encoder.{b}.{r}.fn.4.net.{0,2}.{weight,bias}        its SqueezeExcite (squeeze_excite=True only; decoder units alike)
     {encoder,decoder}_film.to_cond.{weight,bias}        FiLM conditioners (with_film=True only)
+    {encoder,decoder}.{2 b}.fn.fn.{norm.gamma, to_qkva.0.weight}   gate-loop block after block b (with_gate_loop=True only: the blocks then sit at the
+                                                        odd indices 2 b - 1 and the final conv at 2 * len(strides) + 1)
     encoder.{b}.3.conv.{weight,bias}                    strided down-sampling conv (k = 2 * stride)
     encoder.{last}.conv.{weight,bias}                   CausalConv1d(-> codebook_dim, 3)
     {encoder,decoder}_attn.layers.{i}.0.{norm.{weight,bias}, to_qkv.weight, q_scale, k_scale, attn_fn.rel_pos.inv_freq, to_v_gate.0.{weight,bias},
@@ -202,6 +206,88 @@ def DecoderBlock(chan_in, chan_out, stride, cycle_dilations=(1, 3, 9), squeeze_e
                          ResidualUnit(chan_out, chan_out, next(it), squeeze_excite=squeeze_excite, pad_mode=pad_mode),
                          ResidualUnit(chan_out, chan_out, next(it), squeeze_excite=squeeze_excite, pad_mode=pad_mode),
                          ResidualUnit(chan_out, chan_out, next(it), squeeze_excite=squeeze_excite, pad_mode=pad_mode))
+
+
+class _RMSNorm(nn.Module):                                       # gateloop_transformer's RMSNorm: holder of `gamma`
+    def __init__(self, dim):
+        super().__init__()
+        self.gamma = nn.Parameter(torch.ones(dim))
+
+
+class _Rearrange(nn.Module):                                     # `to_qkva.1` of the package ('b n (qkva d) -> qkva (b d) n'): no parameters
+    def forward(self, x):
+        raise NotImplementedError('runs inside the gate-loop scan (csrc/gate_loop.hip): the q | kv | a rows of z')
+
+
+class SimpleGateLoopLayer(nn.Module):
+    """holder of gateloop_transformer.SimpleGateLoopLayer's parameters (`norm.gamma`, `to_qkva.0.weight`) in the one configuration the reference
+    builds: prenorm RMSNorm, no post_ln, forward in time.  `use_heinsen` (the log-space formulation of the same recurrence) selects no different
+    arithmetic here: both of the reference's call sites run the one scan kernel.  The arithmetic is RESTATED (tests/gate_loop_restated.py; the package
+    is not vendored, parity with it is unpinned, like LocalMHA, FSQ and LFQ)."""
+
+    def __init__(self, dim, use_heinsen=False, post_ln=False, reverse=False):
+        super().__init__()
+        if post_ln:
+            raise NotImplementedError('SimpleGateLoopLayer(post_ln=True) is not implemented (the reference builds the default False)')
+        if reverse:
+            raise NotImplementedError('SimpleGateLoopLayer(reverse=True) is not implemented (the reference builds the default False)')
+        self.dim = dim
+        self.norm = _RMSNorm(dim)
+        self.to_qkva = nn.Sequential(nn.Linear(dim, dim * 3, bias=False), _Rearrange())
+        self._lin = _Linear1x1()                                 # packed images of to_qkva.0.weight, per parameter version
+
+    def forward(self, x, cache=None, return_cache=False):
+        raise NotImplementedError('SimpleGateLoopLayer runs inside its GateLoopBlock in the codec layout; the streaming protocol (cache= / '
+                                  'return_cache) is not implemented')
+
+
+class ChannelTranspose(nn.Module):                               # soundstream.py:322-330 (holder: `fn`); its skip add is one of the block's two
+    def __init__(self, fn):
+        super().__init__()
+        self.fn = fn
+
+    def forward(self, x, **kwargs):
+        raise NotImplementedError('runs inside its GateLoopBlock: the codec layout [B, C, T] is kept, nothing is transposed')
+
+
+class Residual(nn.Module):                                       # soundstream.py:314-320
+    """Residual(ChannelTranspose(GateLoop(dim))) as ONE op on x fp32 [B, dim, T]: y = q * h + 2 x (each wrapper adds x once), with
+    (q | kv | a) = to_qkva(RMSNorm(x)) and h[t] = sigmoid(a[t]) h[t-1] + kv[t].  Launches: alm_gate_loop_norm_fwd, the k = 1 projection on the
+    exact-fp32 MFMA conv kernel, alm_gate_loop_scan_fwd.  In training mode with a graph wanted: codec_bwd.GateLoopFn over the same launches."""
+
+    def __init__(self, fn):
+        super().__init__()
+        if not (isinstance(fn, ChannelTranspose) and isinstance(fn.fn, SimpleGateLoopLayer)):
+            raise NotImplementedError('Residual: only the reference\'s Residual(ChannelTranspose(GateLoop(dim))) is implemented')
+        self.fn = fn
+
+    @property
+    def layer(self):
+        return self.fn.fn
+
+    def launches(self, x):
+        """(z = to_qkva(RMSNorm(x)) [B, 3 dim, T], y): the forward launches, shared by the eval path and the autograd Function"""
+        layer = self.layer
+        xn = ops.gate_loop_norm_fwd(x, layer.norm.gamma.detach().to(F32).contiguous())
+        z = layer._lin(layer.to_qkva[0], xn)
+        return z, ops.gate_loop_scan_fwd(z, x)
+
+    def forward(self, x, **kwargs):
+        if kwargs:
+            raise NotImplementedError(f'GateLoopBlock: the streaming protocol ({", ".join(sorted(kwargs))}) is not implemented')
+        if not x.is_cuda:
+            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
+        x = x.to(F32).contiguous()
+        if x.dim() != 3 or x.shape[1] != self.layer.dim:
+            raise ValueError(f'GateLoopBlock: expected [B, {self.layer.dim}, T], got {tuple(x.shape)}')
+        if codec_bwd.wants_grad(self, x):
+            return codec_bwd.GateLoopFn.apply(x, self.layer.norm.gamma, self.layer.to_qkva[0].weight, self)
+        return self.launches(x)[-1]
+
+
+def GateLoopBlock(dim, use_heinsen=False):
+    """the reference's wrapped gate-loop layer; state_dict: fn.fn.norm.gamma (dim,), fn.fn.to_qkva.0.weight (3 dim, dim)"""
+    return Residual(ChannelTranspose(SimpleGateLoopLayer(dim, use_heinsen=use_heinsen)))
 
 
 class _EuclideanCodebook(nn.Module):
@@ -811,14 +897,18 @@ class SoundStream(nn.Module):
                  attn_xpos_scale_base=None, attn_dynamic_pos_bias=False, use_gate_loop_layers=False, squeeze_excite=False, pad_mode='reflect',
                  stft_discriminator=None, with_discriminators=False, stft_normalized=False, complex_stft_discr_logits_abs=True,
                  complex_stft_discr_kwargs: dict = {}, with_mel_loss=False, multi_spectral_window_powers_of_two=tuple(range(6, 12)),
-                 multi_spectral_n_ffts=512, multi_spectral_n_mels=64, with_grad_penalty=False, with_film=False, with_lfq=False, **kwargs):
+                 multi_spectral_n_ffts=512, multi_spectral_n_mels=64, with_grad_penalty=False, with_film=False, with_lfq=False, with_gate_loop=False,
+                 **kwargs):
         super().__init__()
         assert not (use_lookup_free_quantizer and use_finite_scalar_quantizer)                       # soundstream.py:555
         if use_lookup_free_quantizer and not with_lfq:
             raise NotImplementedError('the lookup-free quantizer (LFQ, use_lookup_free_quantizer=True) is opt-in in this port: pass with_lfq=True '
                                       '(GroupedResidualLFQ; its arithmetic is restated from the paper, parity with the installed package is unpinned)')
-        if use_gate_loop_layers or rq_stochastic_sample_codes:
-            raise NotImplementedError('gate-loop layers / stochastic code sampling are not implemented (reference defaults False)')
+        if use_gate_loop_layers and not with_gate_loop:
+            raise NotImplementedError('the gate-loop layers (use_gate_loop_layers=True) are opt-in in this port: pass with_gate_loop=True '
+                                      '(GateLoopBlock; the layer\'s arithmetic is restated, parity with the gateloop_transformer package is unpinned)')
+        if rq_stochastic_sample_codes:
+            raise NotImplementedError('stochastic code sampling (rq_stochastic_sample_codes=True) is not implemented (reference default False)')
         self.use_lookup_free_quantizer = bool(use_lookup_free_quantizer)
         self.use_finite_scalar_quantizer = bool(use_finite_scalar_quantizer)
         if use_lookup_free_quantizer:                                                                # soundstream.py:561
@@ -836,7 +926,11 @@ class SoundStream(nn.Module):
         self.strides = strides
         layer_channels = (channels, *[m * channels for m in channel_mults])
         pairs = tuple(zip(layer_channels[:-1], layer_channels[1:]))
-        blocks = [EncoderBlock(ci, co, s, enc_cycle_dilations, squeeze_excite, pad_mode) for (ci, co), s in zip(pairs, strides)]
+        # the gate-loop layers (soundstream.py:524-525, 620-621): one GateLoopBlock after every EncoderBlock (its chan_out) and DecoderBlock (its chan_in)
+        self.use_gate_loop_layers = bool(use_gate_loop_layers)
+        gate_loop = (lambda dim: (GateLoopBlock(dim),)) if self.use_gate_loop_layers else (lambda dim: ())
+        blocks = [m for (ci, co), s in zip(pairs, strides)
+                  for m in (EncoderBlock(ci, co, s, enc_cycle_dilations, squeeze_excite, pad_mode), *gate_loop(co))]
         self.encoder = nn.Sequential(CausalConv1d(input_channels, channels, 7, pad_mode=pad_mode), *blocks,
                                      CausalConv1d(layer_channels[-1], codebook_dim, 3, pad_mode=pad_mode))
         attn_kwargs = dict(dim=codebook_dim, dim_head=attn_dim_head, heads=attn_heads, depth=attn_depth, window_size=attn_window_size,
@@ -851,7 +945,8 @@ class SoundStream(nn.Module):
             self.decoder_film = FiLM(codebook_dim, dim_cond=2)
         dec_cycle_dilations = kwargs.pop('dec_cycle_dilations', (1, 3, 9))          # remaining kwargs: attention / discriminator / loss options of
                                                                                     # the parts that are not built here (ignored, like before)
-        dblocks = [DecoderBlock(co, ci, s, dec_cycle_dilations, squeeze_excite, pad_mode) for (ci, co), s in reversed(tuple(zip(pairs, strides)))]
+        dblocks = [m for (ci, co), s in reversed(tuple(zip(pairs, strides)))
+                   for m in (DecoderBlock(co, ci, s, dec_cycle_dilations, squeeze_excite, pad_mode), *gate_loop(ci))]
         self.decoder = nn.Sequential(CausalConv1d(codebook_dim, layer_channels[-1], 7, pad_mode=pad_mode), *dblocks,
                                      CausalConv1d(channels, input_channels, 7, pad_mode=pad_mode))             # soundstream.py:615-627
         self.num_quantizers = rq_num_quantizers
@@ -962,6 +1057,8 @@ class SoundStream(nn.Module):
         for layer in self.encoder:
             if isinstance(layer, CausalConv1d):
                 h = layer.call(h)
+            elif isinstance(layer, Residual):                    # GateLoopBlock (use_gate_loop_layers=True)
+                h = layer(h)
             else:
                 for sub in layer:
                     h = sub(h) if isinstance(sub, _ResidualFn) else sub.call(h)
@@ -1174,6 +1271,8 @@ class SoundStream(nn.Module):
             for layer in self.decoder:
                 if isinstance(layer, CausalConv1d):
                     h = layer.call(h)
+                elif isinstance(layer, Residual):                            # GateLoopBlock (use_gate_loop_layers=True)
+                    h = layer(h)
                 else:
                     for sub in layer:
                         h = sub(h)

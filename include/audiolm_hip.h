@@ -764,6 +764,30 @@ int alm_lfq_bwd(const float* g, long long ldg, const float* g_loss, const float*
                 long long ws_floats, int M, int dim_g, int d, int Q, int k, float inv_temperature, float entropy_w, float commit_w, float gamma,
                 void* stream);
 
+/* ---- the gate-loop layer of SoundStream(use_gate_loop_layers=True) (csrc/gate_loop.hip; restated in tests/gate_loop_restated.py).  Codec layout
+ * [B][C][T] fp32, time contiguous; exact fp32, no atomics: every output is bitwise reproducible.
+ *   alm_gate_loop_norm_fwd : xn = x r gamma, r[b,t] = sqrt(C) / max(||x[b,:,t]||_2, 1e-12)   (the k = 1 projection z = W xn is alm_conv1d_causal)
+ *   alm_gate_loop_scan_fwd : z [B][3 C][T] (rows q | kv | a) -> h[t] = sigmoid(z_a[t]) h[t-1] + z_kv[t], h[-1] = 0 (so a[0] has no effect);
+ *                            out = z_q h + 2 x, or with h_only out = h (x may be NULL).  A workgroup scans one chunk of alm_gate_loop_chunk() steps
+ *                            of one row (lanes compose 4 consecutive steps, a 64-lane shuffle scan, waves through LDS); rows longer than a chunk
+ *                            take three launches (chunk aggregates, an ordered carry pass per row, apply) and need ws (alm_gate_loop_scan_ws_floats
+ *                            floats, owned by the caller; 0 for rows of at most one chunk, then ws may be NULL).  The chunk length is a constant of
+ *                            the library.  16-byte accesses when T % 4 == 0 and the tensors are 16-byte aligned, scalar ones otherwise.
+ *   alm_gate_loop_scan_bwd : g = dL/dout [B][C][T], z, h (of an h_only forward) -> dz [B][3 C][T]: dq = g h, dkv = dh with
+ *                            dh[t] = g[t] q[t] + a[t+1] dh[t+1] (the same scan from the row's end, gate shifted by one), da = dh h[t-1] a (1 - a),
+ *                            exactly 0 at t = 0.  Without the 2 g of the two skips (alm_gate_loop_norm_bwd adds it).
+ *   alm_gate_loop_norm_bwd : dxn = dL/dxn -> dx = r gamma dxn - x (r^3 / C) sum_k dxn_k gamma_k x_k + 2 g; dgamma [C] = sum_{b,t} dxn x r from
+ *                            per-block partials in ws (alm_gate_loop_norm_bwd_ws_floats floats), added in block order.
+ * Limits: B <= 65535 for the two norm calls, B C ceil(T / chunk) < 2^31 / 3 for the scans; else ALM_ERR_UNSUPPORTED. */
+int alm_gate_loop_chunk(void);
+int alm_gate_loop_norm_fwd(const float* x, const float* gamma, float* xn, int B, int C, int T, void* stream);
+int alm_gate_loop_scan_ws_floats(int B, int C, int T);
+int alm_gate_loop_scan_fwd(const float* z, const float* x, float* out, float* ws, long long ws_floats, int B, int C, int T, int h_only, void* stream);
+int alm_gate_loop_scan_bwd(const float* g, const float* z, const float* h, float* dz, float* ws, long long ws_floats, int B, int C, int T, void* stream);
+int alm_gate_loop_norm_bwd_ws_floats(int B, int C, int T);
+int alm_gate_loop_norm_bwd(const float* dxn, const float* x, const float* gamma, const float* g, float* dx, float* dgamma, float* ws,
+                           long long ws_floats, int B, int C, int T, void* stream);
+
 /* ---- launch lists (round 6): a recorded sequence of the launches above re-issued by ONE host call ---------------------------------------------
  * The depth loop of audiolm_pytorch.py:528-547 (Transformer.forward) and its backward are ~190 launches per training step whose ORDER and scalar arguments
  * depend only on the model configuration and the batch shape; only buffer addresses change between steps.  The host records the sequence once per shape

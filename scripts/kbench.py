@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty] [se_film] [fsq] [lfq]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty] [se_film] [fsq] [lfq] [gate_loop]"""
 import os
 import sys
 import time
@@ -1207,6 +1207,87 @@ def bench_lfq():
              'alm_fsq_bwd (2 launches)')
     for name, (med, lo, hi) in zip(names, median(fns)):
         print(f'  {name:28s} {med * 1e3:9.1f} us (min {lo * 1e3:.1f}, max {hi * 1e3:.1f})', flush=True)
+
+
+def bench_gate_loop():
+    """Gate-loop block (csrc/gate_loop.hip) at the default codec's eight stage shapes, batch and clip of the se_film section (8 x 10 s @ 16 kHz):
+    after the encoder blocks C = 64 / 128 / 256 / 512 at T = 80000 / 20000 / 4000 / 500, after the decoder blocks C = 256 / 128 / 64 / 32 at
+    T = 4000 / 20000 / 80000 / 160000 (five distinct shapes, each timed once).  Per shape: the two scan entry points alone with the rate on the bytes
+    they move (forward 20 B per element: z 12, x, y; backward 28 B: g, q, a, h, dz 12), then the whole block, eval forward and training forward +
+    backward, with the rate on the bytes the OP must move (forward 8 B per element: x in, y out; forward + backward 20 B: also g and x in, dx out)
+    against the 6.29 TB/s copy rate of DESIGN section 20.  Then tokenize / decode of the default model without and with the layers.  Interleaved
+    rounds, medians, one event pair per call.  Reported, not gated."""
+    from audiolm_pytorch_amd import soundstream as S
+    COPY = 6290.                                                  # GB/s
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def median(fns, rounds=7, warm=2):
+        for _ in range(warm):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(rounds):
+            for t, fn in zip(ts, fns):
+                t.append(once(fn))
+        return [sorted(t)[len(t) // 2] for t in ts]
+
+    torch.manual_seed(0)
+    B, n = 8, 160000
+    stages = [('enc 1', 64, n // 2), ('enc 2', 128, n // 8), ('enc 3', 256, n // 40), ('enc 4', 512, n // 320),
+              ('dec 1', 256, n // 40), ('dec 2', 128, n // 8), ('dec 3', 64, n // 2), ('dec 4', 32, n)]
+    print(f'chunk {ops.GATE_LOOP_CHUNK}; {"stage":6s} {"shape":18s} {"scan fwd":>9s} {"GB/s":>6s} {"scan bwd":>9s} {"GB/s":>6s} | {"block fwd":>9s} {"GB/s":>6s} '
+          f'{"of copy":>7s} | {"block f+b":>9s} {"GB/s":>6s} {"of copy":>7s}', flush=True)
+    done = {}
+    for name, C, T in stages:
+        if (C, T) not in done:
+            x, g = torch.randn(B, C, T, device=dev), torch.randn(B, C, T, device=dev)
+            block = S.GateLoopBlock(C).to(dev)
+            with torch.no_grad():
+                z = block.launches(x)[0]
+            h = ops.gate_loop_scan_fwd(z)
+            xg = x.detach().requires_grad_()
+
+            def fwd():
+                with torch.no_grad():
+                    return block.eval()(x)
+
+            def step():
+                block.train().zero_grad(set_to_none=True)
+                xg.grad = None
+                block(xg).backward(g)
+
+            done[(C, T)] = median([lambda: ops.gate_loop_scan_fwd(z, x), lambda: ops.gate_loop_scan_bwd(g, z, h), fwd, step]) + [x.numel() / 1e6]
+            del x, g, z, h, xg, block
+        t_sf, t_sb, t_f, t_s, me = done[(C, T)]
+        print(f'{"":11s}{name:6s} {f"C={C} T={T}":18s} {t_sf:9.3f} {20 * me / t_sf:6.0f} {t_sb:9.3f} {28 * me / t_sb:6.0f} | {t_f:9.3f} {8 * me / t_f:6.0f} '
+              f'{8 * me / t_f / COPY:7.1%} | {t_s:9.3f} {20 * me / t_s:6.0f} {20 * me / t_s / COPY:7.1%}', flush=True)
+    wave = torch.randn(B, n, device=dev) * 0.3
+    gen = torch.Generator().manual_seed(5)
+    rows = []
+    for label, kw in (('without', {}), ('with gate-loop layers', dict(use_gate_loop_layers=True, with_gate_loop=True))):
+        ss = A.SoundStream(codebook_size=1024, rq_num_quantizers=8, **kw)
+        for layer in ss.rq.rvqs[0].layers:
+            layer._codebook.embed.copy_(torch.randn(layer._codebook.embed.shape, generator=gen) * 0.5)
+            layer._codebook.initted.fill_(True)
+        ss.to(dev)
+        codes = ss.tokenize(wave)
+
+        def decode():
+            with torch.no_grad():
+                return ss.decode_from_codebook_indices(codes)
+
+        rows.append((label, median([lambda: ss.tokenize(wave), decode], rounds=5)))
+        del ss
+    for label, (t_tok, t_dec) in rows:
+        print(f'default SoundStream, {B} x {n} samples, {label:22s}: tokenize {t_tok:8.2f} ms   decode {t_dec:8.2f} ms', flush=True)
 
 
 if __name__ == '__main__':
