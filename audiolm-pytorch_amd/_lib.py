@@ -83,6 +83,8 @@ SIGNATURES = {
     'alm_hc_partial_width': [_I, _I],
     'alm_hc_grads_width': [_I, _I],
     'alm_hc_partial_rows': [_I, _I, _I, _I, _L, _I],
+    'alm_hc_fwd_prefetch': [_I, _I, _I],
+    'alm_hc_bwd_variant': [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _I],
     'alm_hc_fwd': [_P, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     'alm_hc_bwd': [_P, _I, _I, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _L, _P, _P, _L, _P, _I, _I, _I, _I, _I, _P],
     'alm_hc_param_grads': [_P, _I, _P, _P, _P, _P, _I, _I, _P],

@@ -1459,10 +1459,14 @@ void launch_fwd_p(const HcFwdArgs& a, hipStream_t st) {
     if (!resident) resident = resident_blocks(k);
     hipLaunchKernelGGL(k, dim3(hc_grid((long long)a.B * a.N, 4 / WPT, resident)), dim3(256), 0, st, a);
 }
+// the forward's variant choice (launch_fwd_w and the alm_hc_fwd_prefetch query): the software-prefetching kernel takes bf16 stream tensors of a width
+// that fills every lane of the token's waves (PF assumes no out-of-range lanes)
+bool hc_fwd_route_pf(bool r_bf16, bool rin_bcast, int D) { return r_bf16 && !rin_bcast && D == hc_wpt(D) * 256; }
+
 template <typename RT, int S, int WPT, bool DEPTH, bool WIDTH, bool FINAL>
 void launch_fwd_w(const HcFwdArgs& a, hipStream_t st) {
     if constexpr (sizeof(RT) == 2) {
-        if (!a.rin_bcast && a.D == WPT * 256) return launch_fwd_p<RT, S, WPT, DEPTH, WIDTH, FINAL, true>(a, st);      // PF assumes no out-of-range lanes
+        if (hc_fwd_route_pf(true, a.rin_bcast != 0, a.D)) return launch_fwd_p<RT, S, WPT, DEPTH, WIDTH, FINAL, true>(a, st);
     }
     launch_fwd_p<RT, S, WPT, DEPTH, WIDTH, FINAL, false>(a, st);
 }
@@ -1526,25 +1530,33 @@ int bwd_grid(long long M, int D) {
     if (wpt == 2) return bwd_grid_w<RT, S, 2, WIDTH, DEPTH, LNF>(M, D);
     return bwd_grid_w<RT, S, 4, WIDTH, DEPTH, LNF>(M, D);
 }
+// the backward's variant choice (launch_bwd_w and the alm_hc_bwd_variant query): -1 = the plain kernel, 0 / 1 / 2 = the prefetching kernel with stream
+// tensors everywhere / broadcast dRn / broadcast R, 3 = the LDS-DMA kernel.  ld_max: the largest row stride of dx / dxn / extra / y / dy; al16: every row the
+// LDS-DMA kernel reads (dRn, R, dxn, extra, y: bases and row strides) starts on a 16-byte boundary, and coef_prev / dbeta are given.
+int hc_bwd_route(bool r_bf16, int S, bool width, bool depth, bool lnf, long long B, long long N, int D, bool bcast, bool r_bcast, bool has_dR, bool has_dsum,
+                 long long ld_max, bool al16) {
+    // prefetching variants (bf16 streams, every lane in range): bc 0 plain, 1 broadcast dRn, 2 broadcast R; both broadcast: the plain kernel
+    int bc = -1;
+    if (!r_bf16) return bc;
+    const int wpt = hc_wpt(D);
+    const long long M = B * N;
+    // the prefetching kernels address with 32-bit byte offsets: every tensor below 4 GB (the largest: fp32 [M][D] / RT [B][S][N][D] / the coefficient records)
+    const bool small = B * S * N * D * 4 < 0xffffffffLL && M * 64 * 4 < 0xffffffffLL && M * ld_max * 4 < 0xffffffffLL;
+    if (small && D == wpt * 256 && !(bcast && r_bcast)) bc = bcast ? 1 : ((r_bcast && width) ? 2 : (r_bcast ? -1 : 0));
+    // the prefetching kernels with stream-tensor R store dR unconditionally and never the stream sum (see STRAIGHT): any other request -> plain kernel
+    if (width && (bc == 0 || bc == 1) && (!has_dR || has_dsum)) bc = -1;
+    // the LDS-DMA variant moves 16-byte pieces: every row it reads must start on a 16-byte boundary (bases and row strides)
+    if (width && depth && lnf && wpt == 4 && S == 4 && bc == 0 && al16 && hc_gl_enabled()) bc = 3;
+    return bc;
+}
 template <typename RT, int S, int WPT, bool WIDTH, bool DEPTH, bool LNF>
 void launch_bwd_w(const HcBwdArgs& a, hipStream_t st) {
     const long long M = (long long)a.B * a.N;
     const int rows_alloc = (4 / WPT) * bwd_grid_w<RT, S, WPT, WIDTH, DEPTH, LNF>(M, a.D);     // what alm_hc_partial_rows reported
-    // prefetching variants (bf16 streams, every lane in range): bc 0 plain, 1 broadcast dRn, 2 broadcast R; both broadcast: the plain kernel
-    int bc = -1;
-    if constexpr (sizeof(RT) == 2) {
-        // the prefetching kernels address with 32-bit byte offsets: every tensor below 4 GB (the largest: fp32 [M][D] / RT [B][S][N][D] / the coefficient records)
-        const bool small = (long long)a.B * S * a.N * a.D * 4 < 0xffffffffLL && M * 64 * 4 < 0xffffffffLL && M * (long long)std::max(std::max(std::max(a.lddxn, a.ldex), std::max(a.ldy, a.lddy)), a.lddx) * 4 < 0xffffffffLL;
-        if (small && a.D == WPT * 256 && !(a.bcast && a.r_bcast)) bc = a.bcast ? 1 : ((a.r_bcast && WIDTH) ? 2 : (a.r_bcast ? -1 : 0));
-        // the prefetching kernels with stream-tensor R store dR unconditionally and never the stream sum (see STRAIGHT): any other request -> plain kernel
-        if (WIDTH && (bc == 0 || bc == 1) && (!a.dR || a.dsum)) bc = -1;
-        if constexpr (WIDTH && DEPTH && LNF && WPT == 4 && S == 4) {
-            // the LDS-DMA variant moves 16-byte pieces: every row it reads must start on a 16-byte boundary (bases and row strides)
-            const bool al16 = ((((uintptr_t)a.dRn | (uintptr_t)a.R | (uintptr_t)a.dxn | (uintptr_t)a.extra | (uintptr_t)a.y) & 15) == 0) &&
-                              (((a.lddxn | a.ldex | a.ldy) & 7) == 0) && a.coef_prev && a.dbeta;
-            if (bc == 0 && al16 && hc_gl_enabled()) bc = 3;
-        }
-    }
+    const bool al16 = ((((uintptr_t)a.dRn | (uintptr_t)a.R | (uintptr_t)a.dxn | (uintptr_t)a.extra | (uintptr_t)a.y) & 15) == 0) &&
+                      (((a.lddxn | a.ldex | a.ldy) & 7) == 0) && a.coef_prev && a.dbeta;
+    const int bc = hc_bwd_route(sizeof(RT) == 2, S, WIDTH, DEPTH, LNF, a.B, a.N, a.D, a.bcast != 0, a.r_bcast != 0, a.dR != nullptr, a.dsum != nullptr,
+                                std::max(std::max(std::max(a.lddxn, a.ldex), std::max(a.ldy, a.lddy)), a.lddx), al16);
     int grid = bwd_grid_p<RT, S, WPT, WIDTH, DEPTH, LNF, false>(M, a.D);
     if constexpr (sizeof(RT) == 2) {
         if (bc == 0) grid = bwd_grid_p<RT, S, WPT, WIDTH, DEPTH, LNF, true, 0>(M, a.D);
@@ -1625,6 +1637,26 @@ extern "C" int alm_hc_grads_width(int S, int D) { return D * (S + 4) + S * (S + 
 extern "C" int alm_hc_partial_rows(int mode, int fused_ln, int r_bf16, int S, long long tokens, int D) {
     return r_bf16 ? bwd_rows_s<bf16_t>(mode, fused_ln != 0, S, tokens, D) : bwd_rows_s<float>(mode, fused_ln != 0, S, tokens, D);
 }
+/* which kernel variant a launch takes (the launchers call the same two host functions): what the tests assert about the case they mean to exercise */
+extern "C" int alm_hc_fwd_prefetch(int r_bf16, int rin_bcast, int D) {
+    if ((D & 3) || D < 4 || D > 1024) return 0;
+    return hc_fwd_route_pf(r_bf16 != 0, rin_bcast != 0, D) ? 1 : 0;
+}
+extern "C" int alm_hc_bwd_variant(int mode, int fused_ln, int r_bf16, int S, int B, int N, int D, int dRn_bcast, int r_bcast, int want_dR, int want_dsum,
+                                  long long ld_max, int aligned16) {
+    if (mode < 1 || mode > 3 || S < 2 || S > 4 || B < 1 || N < 1 || (D & 3) || D < 4 || D > 1024) return -1;
+    return hc_bwd_route(r_bf16 != 0, S, (mode & 2) != 0, (mode & 1) != 0, (mode & 2) && fused_ln, B, N, D, dRn_bcast != 0, r_bcast != 0, want_dR != 0,
+                        want_dsum != 0, ld_max, aligned16 != 0);
+}
+
+namespace {
+// base-pointer alignment the kernels' vector accesses take for granted (row strides are multiples of 4 elements): 16 bytes for fp32 rows (float4),
+// 8 bytes for bf16 rows (uint2); NULL passes (an optional tensor that is not given).  Not checked: the float tensors read or written one element at a
+// time (coef, mean, rstd, dbeta ..: any float* will do), and `partial` -- its rows are alm_hc_partial_width floats apart, 2 mod 4 for S = 4, so the
+// float4 stores of every odd row sit on 8-byte boundaries whatever the base: the kernels rely on gfx9 global memory taking a 16-byte access at
+// 4-byte alignment (unaligned access mode), as they have from the start.
+bool hc_al(const void* p, int bytes) { return ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }
+}  // namespace
 
 // mode: 1 = depth connection only (-> R_out), 2 = width connection only, 3 = depth (previous branch) + width (next branch) fused,
 //       5 = depth + stream sum + final LayerNorm (-> xs_out fp32, xn_out bf16 or xn32_out fp32, mean, rstd; R_out is not written)
@@ -1634,6 +1666,14 @@ extern "C" int alm_hc_fwd(const void* R_in, int rin_bcast, int r_bf16, const voi
                           const float* Bb, const float* ln_gamma, void* x_out, long long ldx, void* xn_out, long long ldxn, float* xn32_out,
                           float* mean, float* rstd, float* coef, float* xs_out, int mode, int B, int S, int N, int D, void* stream) {
     if ((D & 3) || D > 1024 || (ldx & 3) || (ldxn & 3) || (ldy & 3)) return ALM_ERR_BAD_ARG;
+    if (B < 1 || N < 1 || D < 4 || !R_in) return ALM_ERR_BAD_ARG;                   // (an empty launch: grid 0, and the kernel divides by N)
+    if (mode != 1 && mode != 2 && mode != 3 && mode != 5) return ALM_ERR_BAD_ARG;
+    {
+        const int rb = r_bf16 ? 8 : 16;
+        if (!hc_al(R_in, rin_bcast ? 16 : rb) || !hc_al(R_out, rb) || !hc_al(y_prev, 8) || !hc_al(x_out, 8) || !hc_al(xn_out, 8) || !hc_al(xn32_out, 16) ||
+            !hc_al(xs_out, 16) || !hc_al(ln_gamma, 16))
+            return ALM_ERR_BAD_ARG;
+    }
     if ((mode & 1) && (!y_prev || !coef_prev || (!(mode & 4) && !R_out))) return ALM_ERR_BAD_ARG;
     if ((mode & 2) && (!hc_gamma || !Wa || !sa || !Aa || !wb || !sb || !Bb || !ln_gamma || !xn_out || !mean || !rstd || !coef)) return ALM_ERR_BAD_ARG;
     if ((mode & 4) && (!ln_gamma || !(xn_out || xn32_out) || !mean || !rstd || !xs_out)) return ALM_ERR_BAD_ARG;
@@ -1657,6 +1697,14 @@ extern "C" int alm_hc_bwd(const void* dRn, int dRn_bcast, int r_bf16, const floa
                           const float* sb, void* dR, float* dsum, float dsum_scale, float* partial, const void* y_prev, long long ldy, const float* coef_prev, void* dy,
                           long long lddy, float* dbeta_out, int mode, int B, int S, int N, int D, void* stream) {
     if ((D & 3) || D > 1024 || (lddx & 3) || (lddxn & 3) || (ldex & 3) || (ldy & 3) || (lddy & 3) || !dRn) return ALM_ERR_BAD_ARG;
+    if (B < 1 || N < 1 || D < 4) return ALM_ERR_BAD_ARG;                            // (an empty launch: grid 0, and the kernel divides by N)
+    if (mode < 1 || mode > 3) return ALM_ERR_BAD_ARG;
+    {
+        const int rb = r_bf16 ? 8 : 16;
+        if (!hc_al(dRn, dRn_bcast ? 16 : rb) || !hc_al(R, r_bcast ? 16 : rb) || !hc_al(dR, rb) || !hc_al(dsum, 16) || !hc_al(dx, 16) || !hc_al(dxn, 8) ||
+            !hc_al(extra, 8) || !hc_al(ln_gamma, 16) || !hc_al(y_prev, 8) || !hc_al(dy, 8))
+            return ALM_ERR_BAD_ARG;
+    }
     const bool lnf = dxn != nullptr;
     if ((mode & 2) && (!R || !coef || !dbeta || !hc_gamma || !Wa || !sa || !wb || !sb || !(dR || dsum) || !partial)) return ALM_ERR_BAD_ARG;
     if ((mode & 1) && (mode & 2) && !dR) return ALM_ERR_BAD_ARG;

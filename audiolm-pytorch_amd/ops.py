@@ -701,6 +701,15 @@ def hc_fwd(R_in, B, S, N, D, *, y_prev=None, coef_prev=None, hc=None, ln_gamma=N
     return out
 
 
+def _hc_bwd_geometry(D, dx, dxn, extra, hc, y_prev, sum_only, r_dtype):
+    """What hc_bwd hands alm_hc_bwd besides the pointers -- mode, fused-LayerNorm flag, storage flag, the five row strides, which of dR / dsum is asked
+    for -- built in ONE place: hc_bwd launches with it and hc_bwd_variant queries the launcher's route with it."""
+    width, depth = hc is not None, y_prev is not None
+    ld = lambda t: t.stride(0) if t is not None else 0
+    return dict(width=width, depth=depth, mode=(2 if width else 0) | (1 if depth else 0), lnf=int(width and dxn is not None), rbf=int(r_dtype == BF16),
+                lddx=ld(dx), lddxn=ld(dxn), ldex=ld(extra), ldy=ld(y_prev), lddy=D, want_dR=int(width and not sum_only), want_dsum=int(width and sum_only))
+
+
 def hc_bwd(dRn, B, S, N, D, *, bcast=False, dx=None, dxn=None, extra=None, mean=None, rstd=None, ln_gamma=None, R=None, coef=None, dbeta=None,
            hc=None, y_prev=None, coef_prev=None, r_bcast=False, sum_only=False, r_dtype=F32, dsum_scale=1.0, dy_out=None, defer_grads=False):
     """Hyper-connection backward (C ABI: alm_hc_bwd).  dRn: gradient wrt the residual output of a width connection, [B, S, N, D] (r_dtype), or with
@@ -713,13 +722,12 @@ def hc_bwd(dRn, B, S, N, D, *, bcast=False, dx=None, dxn=None, extra=None, mean=
     defer_grads: the parameter gradients are NOT finished here -- `grads` is None and `part` = (partial rows, row count, hc) goes to
     hc_param_grads_batched together with the other branches' (two launches for all of them instead of two per branch).
     -> dict(dR, dsum, grads, dy, dbeta, part)."""
-    width, depth = hc is not None, y_prev is not None
-    mode = (2 if width else 0) | (1 if depth else 0)
+    geo = _hc_bwd_geometry(D, dx, dxn, extra, hc, y_prev, sum_only, r_dtype)
+    width, depth, mode, rbf = geo['width'], geo['depth'], geo['mode'], geo['rbf']
     dev, M = dRn.device, B * N
     _chk(dRn, F32 if bcast else r_dtype)
     if R is not None:
         _chk(R, F32 if r_bcast else r_dtype)
-    rbf = int(r_dtype == BF16)
     dR = dsum = part = dy = dbo = None
     if width:
         assert (dx is None) != (dxn is None)
@@ -727,7 +735,7 @@ def hc_bwd(dRn, B, S, N, D, *, bcast=False, dx=None, dxn=None, extra=None, mean=
             dsum = _new((M, D), dtype=F32, device=dev)
         else:
             dR = _new((B, S, N, D), dtype=r_dtype, device=dev)
-        rows = _lib.query('alm_hc_partial_rows', mode, int(dxn is not None), rbf, S, M, D)
+        rows = _lib.query('alm_hc_partial_rows', mode, geo['lnf'], rbf, S, M, D)
         P = _lib.query('alm_hc_partial_width', S, D)
         part = _new((rows, P), dtype=F32, device=dev)
     if depth:
@@ -735,10 +743,9 @@ def hc_bwd(dRn, B, S, N, D, *, bcast=False, dx=None, dxn=None, extra=None, mean=
         assert dy.shape == (M, D) and dy.dtype == BF16 and dy.is_contiguous()
         dbo = _new((M, S), dtype=F32, device=dev)
     hp = [hc[k].data_ptr() for k in ('gamma', 'Wa', 'sa', 'wb', 'sb')] if width else [None] * 5
-    _lib.call('alm_hc_bwd', dRn.data_ptr(), int(bcast), rbf, _p(dx), dx.stride(0) if dx is not None else 0, _p(dxn),
-              dxn.stride(0) if dxn is not None else 0, _p(extra), extra.stride(0) if extra is not None else 0, _p(mean), _p(rstd), _p(ln_gamma),
-              _p(R), int(r_bcast), _p(coef), _p(dbeta), *hp, _p(dR), _p(dsum), float(dsum_scale), _p(part), _p(y_prev), y_prev.stride(0) if depth else 0, _p(coef_prev), _p(dy), D, _p(dbo),
-              mode, B, S, N, D, _st())
+    _lib.call('alm_hc_bwd', dRn.data_ptr(), int(bcast), rbf, _p(dx), geo['lddx'], _p(dxn), geo['lddxn'], _p(extra), geo['ldex'], _p(mean), _p(rstd),
+              _p(ln_gamma), _p(R), int(r_bcast), _p(coef), _p(dbeta), *hp, _p(dR), _p(dsum), float(dsum_scale), _p(part), _p(y_prev), geo['ldy'],
+              _p(coef_prev), _p(dy), geo['lddy'], _p(dbo), mode, B, S, N, D, _st())
     grads = None
     if width and defer_grads:
         return dict(dR=dR, dsum=dsum, grads=None, dy=dy, dbeta=dbo, part=(part, rows, hc))
@@ -792,6 +799,28 @@ def hc_param_grads_batched(parts, S, D):
         _lib.call('alm_hc_param_grads_batched', arr_p, arr_r, nb, arr_g, arr_wa, arr_wb, ws.data_ptr(), arr_o, S, D, _st())
         out += [_hc_grad_views(g[z], S, D) for z in range(nb)]
     return out
+
+
+HC_BWD_VARIANTS = {-1: 'plain', 0: 'pf0', 1: 'pf1', 2: 'pf2', 3: 'gl'}
+
+
+def hc_fwd_prefetch(D, *, rin_bcast=False, r_dtype=F32):
+    """True when hc_fwd with these arguments launches the software-prefetching kernel (C ABI: alm_hc_fwd_prefetch -- the launcher's own choice)."""
+    return bool(_lib.query('alm_hc_fwd_prefetch', int(r_dtype == BF16), int(rin_bcast), D))
+
+
+def hc_bwd_variant(dRn, B, S, N, D, *, bcast=False, dx=None, dxn=None, extra=None, R=None, dbeta=None, hc=None, y_prev=None, coef_prev=None,
+                   r_bcast=False, sum_only=False, r_dtype=F32, **_):
+    """The kernel variant hc_bwd launches for the same keyword arguments: one of HC_BWD_VARIANTS' names (C ABI: alm_hc_bwd_variant -- the launcher's
+    own choice, asked with the launch geometry hc_bwd itself uses; keywords that do not bear on the route are accepted and ignored)."""
+    geo = _hc_bwd_geometry(D, dx, dxn, extra, hc, y_prev, sum_only, r_dtype)
+    # the launcher's al16: every row the LDS-DMA kernel reads starts on a 16-byte boundary (NULL counts as aligned), coef_prev and dbeta are given
+    al16 = all(t is None or t.data_ptr() % 16 == 0 for t in (dRn, R, dxn, extra, y_prev)) and (geo['lddxn'] | geo['ldex'] | geo['ldy']) % 8 == 0
+    al16 = al16 and coef_prev is not None and dbeta is not None
+    ld_max = max(geo['lddx'], geo['lddxn'], geo['ldex'], geo['ldy'], geo['lddy'])
+    v = _lib.query('alm_hc_bwd_variant', geo['mode'], geo['lnf'], geo['rbf'], S, B, N, D, int(bcast), int(r_bcast), geo['want_dR'], geo['want_dsum'],
+                   ld_max, int(al16))
+    return HC_BWD_VARIANTS[v]
 
 
 # un-fused single-connection forms (kernel tests; the product path uses the fused modes)

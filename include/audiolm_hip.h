@@ -279,7 +279,19 @@ int alm_hc_coef_width(int S);
 int alm_hc_partial_width(int S, int D);
 int alm_hc_grads_width(int S, int D);
 int alm_hc_partial_rows(int mode, int fused_ln, int r_bf16, int S, long long tokens, int D);
-/* forward.  mode 1: depth connection only, R_out[t] = sum_s alpha[s][t+1] R_in[s] + beta[t] y_prev (coef_prev = that branch's record);
+/* Which kernel variant a launch takes -- the host functions the launchers themselves call, no device needed.
+ * alm_hc_fwd_prefetch: 1 = the software-prefetching forward kernel (bf16 streams, no rin_bcast, D == 256 * waves per token), 0 = the plain one.
+ * alm_hc_bwd_variant : -1 = plain kernel, 0 / 1 / 2 = prefetching kernel with stream tensors everywhere / broadcast dRn / broadcast R, 3 = the LDS-DMA
+ *   kernel (S 4, D 1024, bf16, mode 3, fused LayerNorm).  want_dR / want_dsum: dR / dsum != NULL; ld_max: the largest row stride among dx, dxn, extra,
+ *   y_prev, dy; aligned16: dRn, R, dxn, extra, y_prev all start on 16-byte boundaries with row strides that are multiples of 8 elements, and coef_prev
+ *   and dbeta are given.  Arguments alm_hc_bwd refuses give -1. */
+int alm_hc_fwd_prefetch(int r_bf16, int rin_bcast, int D);
+int alm_hc_bwd_variant(int mode, int fused_ln, int r_bf16, int S, int B, int N, int D, int dRn_bcast, int r_bcast, int want_dR, int want_dsum,
+                       long long ld_max, int aligned16);
+/* Both launchers return ALM_ERR_BAD_ARG before any launch for B < 1, N < 1, D < 4, a mode outside {1, 2, 3, 5} (forward) / {1, 2, 3} (backward) and for a
+ * base pointer below the alignment of the kernels' vector accesses: 16 bytes for fp32 rows (fp32 / broadcast streams, xs_out, xn32_out, dsum, dx) and
+ * ln_gamma, 8 bytes for bf16 rows (bf16 streams, y_prev, x_out, xn_out, dxn, extra, dy).
+ * forward.  mode 1: depth connection only, R_out[t] = sum_s alpha[s][t+1] R_in[s] + beta[t] y_prev (coef_prev = that branch's record);
  * mode 2: width connection of a branch (its 7 parameters) + the branch's pre-LayerNorm: x, xn = LN(x) ln_gamma, mean, rstd, coef;
  * mode 3: mode 1 of the previous branch fused with mode 2 of the next one on the freshly computed residual (one pass over R);
  * mode 5: depth connection + stream sum (:551) + final LayerNorm (:555): xs_out fp32 [B*N][D], mean, rstd and the LayerNorm output either as
