@@ -206,6 +206,22 @@ class RvqTrainFn(torch.autograd.Function):
         return dx, None, None
 
 
+def _proj_quant_bwd(ctx, x, g_out, params, group_bwd):
+    """the group loop of FsqFn.backward and LfqFn.backward.  group_bwd(g, g_out columns, x columns, kernel weights or None, dx columns) fills the dx
+    columns and returns group g's parameter gradients (nothing in the identity case); returns what backward returns"""
+    mod = ctx.mod
+    dg = x.shape[1] // mod.groups
+    g_out = g_out.to(F32).contiguous()
+    dx = torch.empty_like(x)
+    per = len(params) // mod.groups                                # 4, or 0 in the identity case
+    grads = []
+    for g in range(mod.groups):
+        sl = slice(g * dg, (g + 1) * dg)
+        grads.extend(group_bwd(g, g_out[:, sl], x[:, sl], mod.kernel_weights(params[per * g:per * g + per]), dx[:, sl]))
+    need = ctx.needs_input_grad
+    return (dx if need[0] else None, None, None, *[gr if need[3 + i] else None for i, gr in enumerate(grads)])
+
+
 class FsqFn(torch.autograd.Function):
     """the grouped residual FSQ (soundstream.GroupedResidualFSQ.run): x [M, dim] -> (out, indices; the indices carry no gradient).  `params`: per
     group project_in.{weight, bias}, project_out.{weight, bias} (nothing in the identity case).  Saved: x, per group the projected input z [M, d] and
@@ -215,7 +231,6 @@ class FsqFn(torch.autograd.Function):
     def forward(ctx, x, mod, k, *params):
         out, idx, zs = mod.run(x, k, save_z=True)
         ctx.mod, ctx.k = mod, k
-        ctx.have_z = [z is not None for z in zs]
         ctx.save_for_backward(x, *[z for z in zs if z is not None], *params)
         ctx.mark_non_differentiable(idx)
         return out, idx
@@ -224,23 +239,10 @@ class FsqFn(torch.autograd.Function):
     def backward(ctx, g_out, _):
         mod, k = ctx.mod, ctx.k
         x, *rest = ctx.saved_tensors
-        nz = sum(ctx.have_z)
-        zs, params = rest[:nz], rest[nz:]
-        M, dim = x.shape
-        dg, d, Q = dim // mod.groups, len(mod.levels), mod.num_quantizers
-        g_out = g_out.to(F32).contiguous()
-        dx = torch.empty_like(x)
+        zs, params = (rest[:mod.groups], rest[mod.groups:]) if rest else ([None] * mod.groups, [])      # identity: neither z nor parameters
         consts = mod._consts(x.device)
-        grads = []
-        for g in range(mod.groups):
-            sl = slice(g * dg, (g + 1) * dg)
-            if ctx.have_z[g]:
-                weights = mod.kernel_weights(params[4 * g:4 * g + 4])
-                grads.extend(ops.fsq_bwd(g_out[:, sl], x[:, sl], zs[g], weights, consts, d, Q, k, dx[:, sl]))
-            else:
-                ops.fsq_bwd(g_out[:, sl], x[:, sl], None, None, consts, d, Q, k, dx[:, sl])
-        need = ctx.needs_input_grad
-        return (dx if need[0] else None, None, None, *[gr if need[3 + i] else None for i, gr in enumerate(grads)])
+        return _proj_quant_bwd(ctx, x, g_out, params, lambda g, go, xg, weights, dxg: ops.fsq_bwd(go, xg, zs[g], weights, consts, mod.proj_dim,
+                                                                                                     mod.num_quantizers, k, dxg))
 
 
 class LfqFn(torch.autograd.Function):
@@ -262,19 +264,9 @@ class LfqFn(torch.autograd.Function):
         mod, k = ctx.mod, ctx.k
         x, *rest = ctx.saved_tensors
         saved, params = rest[:2 * mod.groups], rest[2 * mod.groups:]
-        M, dim = x.shape
-        dg, d, Q = dim // mod.groups, mod.codebook_bits, mod.num_quantizers
-        g_out = g_out.to(F32).contiguous()
         g_losses = g_losses.to(F32).contiguous()
-        dx = torch.empty_like(x)
-        per = len(params) // mod.groups                            # 4, or 0 in the identity case
-        grads = []
-        for g in range(mod.groups):
-            sl = slice(g * dg, (g + 1) * dg)
-            weights = mod.kernel_weights(params[per * g:per * g + per])
-            grads.extend(ops.lfq_bwd(g_out[:, sl], g_losses[g], x[:, sl], saved[2 * g], saved[2 * g + 1], weights, d, Q, k, dx[:, sl], mod.loss_cfg))
-        need = ctx.needs_input_grad
-        return (dx if need[0] else None, None, None, *[gr if need[3 + i] else None for i, gr in enumerate(grads)])
+        return _proj_quant_bwd(ctx, x, g_out, params, lambda g, go, xg, weights, dxg: ops.lfq_bwd(
+            go, g_losses[g], xg, saved[2 * g], saved[2 * g + 1], weights, mod.proj_dim, mod.num_quantizers, k, dxg, mod.loss_cfg))
 
 
 # ---------------------------------------------------------------------------------------------- LocalTransformer (csrc/local_attn_bwd.hip)

@@ -22,6 +22,16 @@ typedef __attribute__((ext_vector_type(4))) short bf16x4;
         if (e__ != hipSuccess) return (int)e__;  \
     } while (0)
 
+// workspace segments start on 16 bytes
+inline long long up4(long long n) { return (n + 3) & ~3LL; }
+
+// rows of a chunk of per-chunk partials: `first` rows, doubled until there are at most max_chunks chunks
+inline int row_chunk(int rows, int first, int max_chunks) {
+    int ch = first;
+    while ((rows + ch - 1) / ch > max_chunks) ch *= 2;
+    return ch;
+}
+
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 
 // round-to-nearest-even fp32 -> bf16 (same rounding as torch's .to(bfloat16)); NaN stays NaN
@@ -52,6 +62,32 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// sum over the 256 threads of a workgroup, the same value and the same order on every run
+__device__ __forceinline__ float block_sum(float v) {
+    __shared__ float part[4];
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// the same in double; red: 4 doubles of LDS
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+    v = wave_sum_d(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double s = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return s;
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

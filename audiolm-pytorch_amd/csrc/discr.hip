@@ -308,15 +308,6 @@ __device__ __forceinline__ float loss_term(int mode, float a, float b) {
     }
 }
 
-__device__ __forceinline__ float block_sum(float v) {
-    __shared__ float part[4];
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
 __global__ __launch_bounds__(256) void loss_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ part, long long n,
                                                            long long span, int mode) {
     const long long lo = (long long)blockIdx.x * span, hi = min(n, lo + span);

@@ -231,14 +231,6 @@ __global__ __launch_bounds__(64) void film_bwd_reduce_kernel(const float* __rest
     db[C + c] = sb;
 }
 
-inline long long up4(long long n) { return (n + 3) & ~3LL; }
-
-inline int film_chunk(int rows) {
-    int ch = 32;
-    while ((rows + ch - 1) / ch > 1024) ch *= 2;
-    return ch;
-}
-
 template <bool FULL>
 int se_fwd_launch(int NJ, dim3 grid, hipStream_t st, const float* u, const float* residual, const float* W1, const float* b1, const float* W2,
                   const float* b2, float* out, int C, int inner, int T) {
@@ -336,7 +328,7 @@ extern "C" int alm_film_fwd(const float* x, const float* W, const float* b, floa
 // floats of the caller-owned workspace of alm_film_bwd: row chunks x 2 x C (chunks of 32 rows, doubled until there are at most 1024 of them)
 extern "C" int alm_film_bwd_ws_floats(int rows, int C) {
     if (rows <= 0 || C <= 0) return 0;
-    const int ch = film_chunk(rows);
+    const int ch = row_chunk(rows, 32, 1024);
     const long long n = (long long)((rows + ch - 1) / ch) * 2 * C;
     return n > 0x7fffffffLL ? -1 : (int)n;
 }
@@ -347,7 +339,7 @@ extern "C" int alm_film_bwd(const float* g, const float* x, const float* W, cons
     const int need = alm_film_bwd_ws_floats(rows, C);
     if (need < 0 || C > (1 << 28)) return ALM_ERR_UNSUPPORTED;
     if (ws_floats < need) return ALM_ERR_BAD_ARG;
-    const int ch = film_chunk(rows), NC = (rows + ch - 1) / ch;
+    const int ch = row_chunk(rows, 32, 1024), NC = (rows + ch - 1) / ch;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(film_bwd_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)NC), dim3(64), 0, st, g, x, W, b, dx, ws, rows, C, ch, cond0, cond1);
     ALM_LAUNCH_CHECK();

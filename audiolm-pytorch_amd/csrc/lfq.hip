@@ -18,96 +18,24 @@
 // with no max pass and no overflow.  Because of the eps clamp the entropy is not the sum of d Bernoulli entropies: all 2^d probabilities are formed,
 // each as ONE product of a low-half (<= 5 bits) and a high-half table entry, and its logarithm as one sum -- no exp / log per code.  All in double.
 //
-// Kernels.  forward: (1) lfq_fwd_kernel, the shape of fsq_fwd_kernel (a workgroup of 4 waves takes 16 rows: dot products over dim_g, the chain with
-// thread <-> (row, j), the projection back); (2) lfq_stats_kernel, grid (row chunks, k + 1 layers): per tile of 16 rows the per-bit values and the two
+// Kernels.  The projections, the tiling and the backward's skeleton are csrc/proj_quant.hpp (LD = 16 lanes per row).  forward: (1) lfq_fwd_kernel:
+// project_in, the chain with thread <-> (row, j), project_out; (2) lfq_stats_kernel, grid (row chunks, k + 1 layers): per tile of 16 rows the per-bit values and the two
 // half tables in LDS, then thread <-> code (4 codes a thread at d = 10) runs over the rows and keeps sum_m p_mc and sum p log max(p, eps) in registers;
 // the chunk's partials go to the caller's workspace; (3) lfq_finish_kernel, one workgroup per layer: adds the chunks in chunk order, writes
 // avg [Q][2^d] and the loss.  backward: (1) lfq_bwd_loss_kernel, grid (M / 64, k + 1), thread <-> row: the row's low-half table in LDS ([entry][row],
 // conflict-free), the high half formed per outer iteration, the d + 1 sums over the codes (u-bar and S_j) in registers; writes g_loss[q] dloss_q/dr_q
-// [Q][M][d]; (2) lfq_bwd_kernel, the shape of fsq_bwd_kernel, adds the layers in layer order; (3) the chunk-order reduction of the parameter gradients.
-#include "common.hpp"
+// [Q][M][d]; (2) lfq_bwd_kernel: proj_bwd with dz = (k + 1) g_z + the layers' loss gradients in layer order; (3) the chunk-order reduction of the
+// parameter gradients.
+#include "proj_quant.hpp"
 #include "../../include/audiolm_hip.h"
 
 namespace {
 
-constexpr int LFQ_MAX_D = 10, LFQ_MAX_DIM = 1024, LFQ_MAX_Q = 32;
-constexpr int LFQ_ROWS = 16;                                       // rows per tile
+constexpr int LFQ_MAX_D = 10;
 constexpr int LFQ_LD = 16;                                         // lanes (and LDS entries) per row in the chain phases: d <= 10 padded to 16
 constexpr int LFQ_HALF = 5;                                        // bits of the low-half table
 constexpr int LFQ_BROWS = 64;                                      // rows (= threads) of a workgroup of lfq_bwd_loss_kernel
 constexpr double LFQ_EPS = 1e-5;
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the 256 threads of a workgroup, the same value and the same order on every run; red: 4 doubles of LDS
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-    v = wave_sum_d(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double s = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return s;
-}
-
-// 4 floats at p[c .. c + 3]; VEC: c < n, n % 4 == 0 and p 16-byte aligned are the launcher's business
-template <bool VEC>
-__device__ __forceinline__ float4 ld4(const float* __restrict__ p, int c, int n) {
-    if constexpr (VEC) {
-        return *reinterpret_cast<const float4*>(p + c);
-    } else {
-        float4 v;
-        v.x = c < n ? p[c] : 0.f;
-        v.y = c + 1 < n ? p[c + 1] : 0.f;
-        v.z = c + 2 < n ? p[c + 2] : 0.f;
-        v.w = c + 3 < n ? p[c + 3] : 0.f;
-        return v;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void st4(float* __restrict__ p, int c, int n, float4 v) {
-    if constexpr (VEC) {
-        *reinterpret_cast<float4*>(p + c) = v;
-    } else {
-        if (c < n) p[c] = v.x;
-        if (c + 1 < n) p[c + 1] = v.y;
-        if (c + 2 < n) p[c + 2] = v.z;
-        if (c + 3 < n) p[c + 3] = v.w;
-    }
-}
-
-// w[cc * D + j] = W [n][D] at row c + cc (0 past row n): the 4 D consecutive floats behind W + c D
-template <int D, bool VEC>
-__device__ __forceinline__ void ld_cols(const float* __restrict__ W, int c, int n, float (&w)[4 * D]) {
-    if constexpr (VEC) {
-        const float4* p = reinterpret_cast<const float4*>(W + (long long)c * D);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            const float4 v = p[i];
-            w[4 * i] = v.x, w[4 * i + 1] = v.y, w[4 * i + 2] = v.z, w[4 * i + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4 * D; ++e) w[e] = c + e / D < n ? W[(long long)c * D + e] : 0.f;
-    }
-}
-
-template <int D, bool VEC>
-__device__ __forceinline__ void st_cols(float* __restrict__ W, int c, int n, const float (&w)[4 * D]) {
-    if constexpr (VEC) {
-        float4* p = reinterpret_cast<float4*>(W + (long long)c * D);
-#pragma unroll
-        for (int i = 0; i < D; ++i) p[i] = make_float4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4 * D; ++e)
-            if (c + e / D < n) W[(long long)c * D + e] = w[e];
-    }
-}
 
 // The forward chain of dimension j of one row, called by ALL 16 lanes of a row (`active` = j < d and the row exists).  Returns zsum[j]; writes the
 // row's indices (idx_row = idx + row * ldi, Q columns, -1 past k), lane q % 16 storing column q
@@ -166,75 +94,16 @@ __device__ __forceinline__ float codes_to_zsum(const long long* __restrict__ idx
     return zs;
 }
 
-// out rows of the tile = W_out zs + b_out, zs [LFQ_ROWS][LFQ_LD] in LDS: wave w takes rows 4 w .. 4 w + 3, a lane 4 columns of every 256
-template <int D, bool VEC>
-__device__ __forceinline__ void project_out(const float* zs, const float* __restrict__ W_out, const float* __restrict__ b_out, float* __restrict__ out,
-                                            long long ldo, long long row0, int M, int dim_g) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int c = lane * 4; c < dim_g; c += 256) {
-        float w[4 * D];
-        ld_cols<D, VEC>(W_out, c, dim_g, w);
-        const float4 b = ld4<VEC>(b_out, c, dim_g);
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int r = wave * 4 + rr;
-            const long long row = row0 + r;
-            if (row < M) {
-                float4 o = b;
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    const float zj = zs[r * LFQ_LD + j];
-                    o.x = fmaf(w[j], zj, o.x);
-                    o.y = fmaf(w[D + j], zj, o.y);
-                    o.z = fmaf(w[2 * D + j], zj, o.z);
-                    o.w = fmaf(w[3 * D + j], zj, o.w);
-                }
-                st4<VEC>(out + row * ldo, c, dim_g, o);
-            }
-        }
-    }
-}
-
 // grid ceil(M / 16), 256 threads
 template <int D, bool VEC>
 __global__ __launch_bounds__(256) void lfq_fwd_kernel(const float* __restrict__ x, long long ldx, const float* __restrict__ W_in,
                                                       const float* __restrict__ b_in, const float* __restrict__ W_out, const float* __restrict__ b_out,
                                                       long long* __restrict__ idx, long long ldi, float* __restrict__ out, long long ldo,
                                                       double* __restrict__ z_out, int M, int dim_g, int Q, int k) {
-    __shared__ double zl[LFQ_ROWS * LFQ_LD];
-    __shared__ float zs[LFQ_ROWS * LFQ_LD];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long row0 = (long long)blockIdx.x * LFQ_ROWS;
-    {
-        double acc[4][D];                                          // fp32 products are exact in double: z is the float64 dot product
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-            for (int j = 0; j < D; ++j) acc[rr][j] = 0.0;
-        for (int c = lane * 4; c < dim_g; c += 256) {
-            float4 w[D];
-#pragma unroll
-            for (int j = 0; j < D; ++j) w[j] = ld4<VEC>(W_in + (long long)j * dim_g, c, dim_g);
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const long long row = row0 + wave * 4 + rr;
-                if (row < M) {
-                    const float4 xv = ld4<VEC>(x + row * ldx, c, dim_g);
-#pragma unroll
-                    for (int j = 0; j < D; ++j)
-                        acc[rr][j] = fma((double)xv.w, (double)w[j].w, fma((double)xv.z, (double)w[j].z,
-                                         fma((double)xv.y, (double)w[j].y, fma((double)xv.x, (double)w[j].x, acc[rr][j]))));
-                }
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                const double v = wave_sum_d(acc[rr][j]);
-                if (lane == rr * D + j) zl[(wave * 4 + rr) * LFQ_LD + j] = v + (double)b_in[j];
-            }
-    }
+    __shared__ double zl[PQ_ROWS * LFQ_LD];
+    __shared__ float zs[PQ_ROWS * LFQ_LD];
+    const long long row0 = (long long)blockIdx.x * PQ_ROWS;
+    project_in<D, VEC, LFQ_LD>(x, ldx, W_in, b_in, zl, row0, M, dim_g);
     __syncthreads();
     {
         const int r = threadIdx.x >> 4, j = threadIdx.x & 15;
@@ -246,7 +115,7 @@ __global__ __launch_bounds__(256) void lfq_fwd_kernel(const float* __restrict__ 
         if (j < D) zs[r * LFQ_LD + j] = zsum;
     }
     __syncthreads();
-    project_out<D, VEC>(zs, W_out, b_out, out, ldo, row0, M, dim_g);
+    project_out<D, VEC, LFQ_LD>(zs, W_out, b_out, out, ldo, row0, M, dim_g);
 }
 
 // dim_g == d, no projections: thread <-> (row, j), 16 rows per workgroup
@@ -254,7 +123,7 @@ __global__ __launch_bounds__(256) void lfq_fwd_identity_kernel(const float* __re
                                                                float* __restrict__ out, long long ldo, double* __restrict__ z_out, int M, int d, int Q,
                                                                int k) {
     const int j = threadIdx.x & 15;
-    const long long row = (long long)blockIdx.x * LFQ_ROWS + (threadIdx.x >> 4);
+    const long long row = (long long)blockIdx.x * PQ_ROWS + (threadIdx.x >> 4);
     const bool active = j < d && row < M;
     const double zv = active ? (double)x[row * ldx + j] : 0.0;
     if (z_out && active) z_out[row * d + j] = zv;
@@ -266,21 +135,21 @@ template <int D, bool VEC>
 __global__ __launch_bounds__(256) void lfq_decode_kernel(const long long* __restrict__ idx, long long ldi, const float* __restrict__ W_out,
                                                          const float* __restrict__ b_out, float* __restrict__ out, long long ldo, int M, int dim_g,
                                                          int ncols) {
-    __shared__ float zs[LFQ_ROWS * LFQ_LD];
-    const long long row0 = (long long)blockIdx.x * LFQ_ROWS;
+    __shared__ float zs[PQ_ROWS * LFQ_LD];
+    const long long row0 = (long long)blockIdx.x * PQ_ROWS;
     {
         const int r = threadIdx.x >> 4, j = threadIdx.x & 15;
         const long long row = row0 + r;
         if (j < D) zs[r * LFQ_LD + j] = row < M ? codes_to_zsum(idx + row * ldi, ncols, j, D) : 0.f;
     }
     __syncthreads();
-    project_out<D, VEC>(zs, W_out, b_out, out, ldo, row0, M, dim_g);
+    project_out<D, VEC, LFQ_LD>(zs, W_out, b_out, out, ldo, row0, M, dim_g);
 }
 
 __global__ __launch_bounds__(256) void lfq_decode_identity_kernel(const long long* __restrict__ idx, long long ldi, float* __restrict__ out,
                                                                   long long ldo, int M, int d, int ncols) {
     const int j = threadIdx.x & 15;
-    const long long row = (long long)blockIdx.x * LFQ_ROWS + (threadIdx.x >> 4);
+    const long long row = (long long)blockIdx.x * PQ_ROWS + (threadIdx.x >> 4);
     if (j < d && row < M) out[row * ldo + j] = codes_to_zsum(idx + row * ldi, ncols, j, d);
 }
 
@@ -295,8 +164,8 @@ __device__ __forceinline__ void bit_logprobs(double a, double& lp, double& lm) {
 // P = sum over the chunk's rows of p_mc, Hs = sum_m sum_c p log max(p, eps) (= - sum_m H(p_m)), Cs = sum_{m,j} (r_q - quant_q)^2
 __global__ __launch_bounds__(256) void lfq_stats_kernel(const double* __restrict__ z, double* __restrict__ ws, int M, int d, int Q, int chunk, int NC,
                                                         double tau2) {
-    __shared__ double pb[LFQ_ROWS][LFQ_MAX_D][2], lb[LFQ_ROWS][LFQ_MAX_D][2];          // per bit: [.][j][1] = P(+), [.][j][0] = P(-)
-    __shared__ double TP[LFQ_ROWS][64], TL[LFQ_ROWS][64];                                // per row: entries 0 .. 31 the low half, 32 .. 63 the high half
+    __shared__ double pb[PQ_ROWS][LFQ_MAX_D][2], lb[PQ_ROWS][LFQ_MAX_D][2];          // per bit: [.][j][1] = P(+), [.][j][0] = P(-)
+    __shared__ double TP[PQ_ROWS][64], TL[PQ_ROWS][64];                                // per row: entries 0 .. 31 the low half, 32 .. 63 the high half
     __shared__ double red[4];
     const int q = blockIdx.y, tid = threadIdx.x;
     const int dl = d < LFQ_HALF ? d : LFQ_HALF, dh = d - dl, nl = 1 << dl, nh = 1 << dh, ncodes = 1 << d;
@@ -304,8 +173,8 @@ __global__ __launch_bounds__(256) void lfq_stats_kernel(const double* __restrict
     const long long r_begin = (long long)blockIdx.x * chunk;
     const long long r_end = r_begin + chunk < M ? r_begin + chunk : M;
     double accp[4] = {0.0, 0.0, 0.0, 0.0}, hs = 0.0, cs = 0.0;
-    for (long long row0 = r_begin; row0 < r_end; row0 += LFQ_ROWS) {
-        const int nrows = r_end - row0 < LFQ_ROWS ? (int)(r_end - row0) : LFQ_ROWS;
+    for (long long row0 = r_begin; row0 < r_end; row0 += PQ_ROWS) {
+        const int nrows = r_end - row0 < PQ_ROWS ? (int)(r_end - row0) : PQ_ROWS;
         {                                                          // (a) thread <-> (row, j): r_q[j], the bit's two probabilities, the commitment term
             const int r = tid >> 4, j = tid & 15;
             if (j < d && r < nrows) {
@@ -473,121 +342,26 @@ __global__ __launch_bounds__(256) void lfq_bwd_kernel(const float* __restrict__ 
                                                       const double* __restrict__ z, const float* __restrict__ gl, const float* __restrict__ W_in,
                                                       const float* __restrict__ W_out, float* __restrict__ dx, long long ldd, float* __restrict__ ws,
                                                       int M, int dim_g, int k, int chunk, long long epad) {
-    __shared__ float gz[LFQ_ROWS * LFQ_LD], dzl[LFQ_ROWS * LFQ_LD], zsl[LFQ_ROWS * LFQ_LD];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int c = threadIdx.x * 4;                                 // this thread's columns in the per-column part (dim_g <= 1024 = 256 x 4)
-    const bool own = c < dim_g;
-    float4 wi[D], a_wi[D];
-    float a_wo[4 * D];
-    float4 a_bo = make_float4(0.f, 0.f, 0.f, 0.f);
-    float a_bi = 0.f;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        wi[j] = own ? ld4<VEC>(W_in + (long long)j * dim_g, c, dim_g) : make_float4(0.f, 0.f, 0.f, 0.f);
-        a_wi[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int e = 0; e < 4 * D; ++e) a_wo[e] = 0.f;
-    const long long r_begin = (long long)blockIdx.x * chunk;
-    const long long r_end = r_begin + chunk < M ? r_begin + chunk : M;
-    for (long long row0 = r_begin; row0 < r_end; row0 += LFQ_ROWS) {
-        {                                                          // g_z = W_out^T g_out: wave <-> 4 rows, lane <-> 4 columns of every 256
-            float acc[4][D];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-                for (int j = 0; j < D; ++j) acc[rr][j] = 0.f;
-            for (int cc = lane * 4; cc < dim_g; cc += 256) {
-                float w[4 * D];
-                ld_cols<D, VEC>(W_out, cc, dim_g, w);
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) {
-                    const long long row = row0 + wave * 4 + rr;
-                    if (row < r_end) {
-                        const float4 gv = ld4<VEC>(g + row * ldg, cc, dim_g);
-#pragma unroll
-                        for (int j = 0; j < D; ++j)
-                            acc[rr][j] = fmaf(gv.w, w[3 * D + j], fmaf(gv.z, w[2 * D + j], fmaf(gv.y, w[D + j], fmaf(gv.x, w[j], acc[rr][j]))));
-                    }
-                }
-            }
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    const float v = wave_sum(acc[rr][j]);
-                    if (lane == rr * D + j) gz[(wave * 4 + rr) * LFQ_LD + j] = v;
-                }
-        }
-        __syncthreads();
-        {                                                          // thread <-> (row, j): dz and zsum, 0 where there is no row
-            const int r = threadIdx.x >> 4, j = threadIdx.x & 15;
-            const long long row = row0 + r;
-            float dzv = 0.f, zsv = 0.f;
-            if (j < D && row < r_end) {
-                dzv = (float)(k + 1) * gz[r * LFQ_LD + j];
-                if (gl)
-                    for (int q = 0; q <= k; ++q) dzv += gl[((long long)q * M + row) * D + j];
-                zsv = chain_zsum(z[row * D + j], k);
-            }
-            dzl[threadIdx.x] = dzv;
-            zsl[threadIdx.x] = zsv;
-        }
-        __syncthreads();
-        if (own) {
-            for (int r = 0; r < LFQ_ROWS; ++r) {
-                const long long row = row0 + r;
-                if (row >= r_end) break;
-                const float4 xv = ld4<VEC>(x + row * ldx, c, dim_g), gv = ld4<VEC>(g + row * ldg, c, dim_g);
-                float4 dd = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    const float dzj = dzl[r * LFQ_LD + j], zsj = zsl[r * LFQ_LD + j];
-                    dd.x = fmaf(dzj, wi[j].x, dd.x), dd.y = fmaf(dzj, wi[j].y, dd.y), dd.z = fmaf(dzj, wi[j].z, dd.z), dd.w = fmaf(dzj, wi[j].w, dd.w);
-                    a_wi[j].x = fmaf(dzj, xv.x, a_wi[j].x), a_wi[j].y = fmaf(dzj, xv.y, a_wi[j].y);
-                    a_wi[j].z = fmaf(dzj, xv.z, a_wi[j].z), a_wi[j].w = fmaf(dzj, xv.w, a_wi[j].w);
-                    a_wo[j] = fmaf(gv.x, zsj, a_wo[j]), a_wo[D + j] = fmaf(gv.y, zsj, a_wo[D + j]);
-                    a_wo[2 * D + j] = fmaf(gv.z, zsj, a_wo[2 * D + j]), a_wo[3 * D + j] = fmaf(gv.w, zsj, a_wo[3 * D + j]);
-                }
-                a_bo.x += gv.x, a_bo.y += gv.y, a_bo.z += gv.z, a_bo.w += gv.w;
-                st4<VEC>(dx + row * ldd, c, dim_g, dd);
-            }
-        }
-        if (threadIdx.x < D)
-            for (int r = 0; r < LFQ_ROWS; ++r) a_bi += dzl[r * LFQ_LD + threadIdx.x];
-        __syncthreads();
-    }
-    float* p = ws + (long long)blockIdx.x * epad;
-    const long long n_w = (long long)D * dim_g;
-    if (own) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) st4<VEC>(p + (long long)j * dim_g, c, dim_g, a_wi[j]);
-        st_cols<D, VEC>(p + n_w, c, dim_g, a_wo);
-        st4<VEC>(p + 2 * n_w, c, dim_g, a_bo);
-    }
-    if (threadIdx.x < D) p[2 * n_w + dim_g + threadIdx.x] = a_bi;
+    proj_bwd<D, VEC, LFQ_LD>(g, ldg, x, ldx, W_in, W_out, dx, ldd, ws, M, dim_g, chunk, epad, [=](long long row, int j, float gzj, float& zsum) {
+        float dz = (float)(k + 1) * gzj;
+        if (gl)
+            for (int q = 0; q <= k; ++q) dz += gl[((long long)q * M + row) * D + j];
+        zsum = chain_zsum(z[row * D + j], k);
+        return dz;
+    });
 }
 
-// thread <-> one element of (dW_in | dW_out | db_out | db_in): the chunks' partials in chunk order
 __global__ __launch_bounds__(64) void lfq_bwd_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dW_in, float* __restrict__ db_in,
                                                             float* __restrict__ dW_out, float* __restrict__ db_out, long long n_w, int dim_g, int d,
                                                             long long epad, int NC) {
-    const long long e = (long long)blockIdx.x * 64 + threadIdx.x;
-    if (e >= 2 * n_w + dim_g + d) return;
-    float s = 0.f;
-#pragma unroll 8
-    for (int i = 0; i < NC; ++i) s += ws[(long long)i * epad + e];
-    if (e < n_w) dW_in[e] = s;
-    else if (e < 2 * n_w) dW_out[e - n_w] = s;
-    else if (e < 2 * n_w + dim_g) db_out[e - 2 * n_w] = s;
-    else db_in[e - 2 * n_w - dim_g] = s;
+    proj_bwd_reduce(ws, dW_in, db_in, dW_out, db_out, n_w, dim_g, d, epad, NC);
 }
 
 // dim_g == d: dx = (k + 1) g + the loss gradients, thread <-> (row, j)
 __global__ __launch_bounds__(256) void lfq_bwd_identity_kernel(const float* __restrict__ g, long long ldg, const float* __restrict__ gl,
                                                                float* __restrict__ dx, long long ldd, int M, int d, int k) {
     const int j = threadIdx.x & 15;
-    const long long row = (long long)blockIdx.x * LFQ_ROWS + (threadIdx.x >> 4);
+    const long long row = (long long)blockIdx.x * PQ_ROWS + (threadIdx.x >> 4);
     if (j < d && row < M) {
         float v = (float)(k + 1) * g[row * ldg + j];
         if (gl)
@@ -596,46 +370,17 @@ __global__ __launch_bounds__(256) void lfq_bwd_identity_kernel(const float* __re
     }
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline long long up4(long long n) { return (n + 3) & ~3LL; }
-inline long long lfq_epad(int dim_g, int d) { return up4(2LL * d * dim_g + dim_g + d); }
+// rows of a chunk of the forward's code-distribution partials: 64, doubled until there are at most 256 chunks
+inline int lfq_stats_chunk(int M) { return row_chunk(M, 64, 256); }
 
-// rows of a chunk of the backward's parameter-gradient partials
-inline int lfq_chunk(int M) {
-    int ch = 32;
-    while ((M + ch - 1) / ch > 1024) ch *= 2;
-    return ch;
-}
-
-// rows of a chunk of the forward's code-distribution partials
-inline int lfq_stats_chunk(int M) {
-    int ch = 64;
-    while ((M + ch - 1) / ch > 256) ch *= 2;
-    return ch;
-}
-
-inline bool lfq_in_limits(int dim_g, int d, int Q) { return d <= LFQ_MAX_D && dim_g <= LFQ_MAX_DIM && Q <= LFQ_MAX_Q; }
-
-#define ALM_LFQ_D(CALL)           \
-    switch (d) {                  \
-        case 1: CALL(1); break;   \
-        case 2: CALL(2); break;   \
-        case 3: CALL(3); break;   \
-        case 4: CALL(4); break;   \
-        case 5: CALL(5); break;   \
-        case 6: CALL(6); break;   \
-        case 7: CALL(7); break;   \
-        case 8: CALL(8); break;   \
-        case 9: CALL(9); break;   \
-        default: CALL(10); break; \
-    }
+#define ALM_LFQ_D(CALL) ALM_PQ_D(LFQ_MAX_D, CALL)
 
 }  // namespace
 
 // doubles of the caller-owned workspace of a training-mode alm_lfq_fwd: row chunks (64 rows, doubled until there are at most 256 chunks) x Q layers
 // x (2^d + 2); -1 outside the limits or past 2^31
 extern "C" int alm_lfq_fwd_ws_doubles(int M, int d, int Q) {
-    if (M <= 0 || d <= 0 || Q <= 0 || !lfq_in_limits(1, d, Q)) return -1;
+    if (M <= 0 || d <= 0 || Q <= 0 || !pq_in_limits(1, d, Q, LFQ_MAX_D)) return -1;
     const int ch = lfq_stats_chunk(M);
     const long long n = (long long)((M + ch - 1) / ch) * Q * ((1LL << d) + 2);
     return n > 0x7fffffffLL ? -1 : (int)n;
@@ -644,10 +389,10 @@ extern "C" int alm_lfq_fwd_ws_doubles(int M, int d, int Q) {
 extern "C" int alm_lfq_fwd(const float* x, long long ldx, const float* W_in, const float* b_in, const float* W_out, const float* b_out, long long* idx,
                            long long ldi, float* out, long long ldo, double* z, float* losses, double* avg, double* ws, long long ws_doubles, int M,
                            int dim_g, int d, int Q, int k, float inv_temperature, float entropy_w, float commit_w, float gamma, void* stream) {
-    if (M <= 0 || dim_g <= 0 || d <= 0 || Q <= 0 || k < 0 || k >= Q || !x || !idx || !out || ldx < dim_g || ldo < dim_g || ldi < Q) return ALM_ERR_BAD_ARG;
-    if (!lfq_in_limits(dim_g, d, Q)) return ALM_ERR_UNSUPPORTED;
-    const bool identity = !W_in && !b_in && !W_out && !b_out;
-    if (identity ? dim_g != d : (!W_in || !b_in || !W_out || !b_out)) return ALM_ERR_BAD_ARG;
+    bool identity, vec;
+    if (const int err = pq_check(idx && ldi >= Q, M, dim_g, d, Q, LFQ_MAX_D, 0, k, Q - 1, {{x, ldx}, {out, ldo}}, {W_in, b_in, W_out, b_out},
+                                 {W_in, W_out, b_out}, identity, vec))
+        return err;
     const int sch = lfq_stats_chunk(M), SNC = (M + sch - 1) / sch;
     if (losses) {
         if (!z || !avg || !ws || !(inv_temperature > 0.f)) return ALM_ERR_BAD_ARG;
@@ -656,11 +401,10 @@ extern "C" int alm_lfq_fwd(const float* x, long long ldx, const float* W_in, con
         if (ws_doubles < need) return ALM_ERR_BAD_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((M + LFQ_ROWS - 1) / LFQ_ROWS));
+    const dim3 grid((unsigned)((M + PQ_ROWS - 1) / PQ_ROWS));
     if (identity) {
         hipLaunchKernelGGL(lfq_fwd_identity_kernel, grid, dim3(256), 0, st, x, ldx, idx, ldi, out, ldo, z, M, d, Q, k);
     } else {
-        const bool vec = dim_g % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && al16(x) && al16(out) && al16(W_in) && al16(W_out) && al16(b_out);
 #define ALM_CALL(N)                                                                                                                                 \
     if (vec) hipLaunchKernelGGL((lfq_fwd_kernel<N, true>), grid, dim3(256), 0, st, x, ldx, W_in, b_in, W_out, b_out, idx, ldi, out, ldo, z, M,     \
                                 dim_g, Q, k);                                                                                                       \
@@ -683,16 +427,14 @@ extern "C" int alm_lfq_fwd(const float* x, long long ldx, const float* W_in, con
 
 extern "C" int alm_lfq_decode(const long long* idx, long long ldi, const float* W_out, const float* b_out, float* out, long long ldo, int M, int dim_g,
                               int d, int Q, int ncols, void* stream) {
-    if (M <= 0 || dim_g <= 0 || d <= 0 || Q <= 0 || ncols <= 0 || ncols > Q || !idx || !out || ldo < dim_g || ldi < ncols) return ALM_ERR_BAD_ARG;
-    if (!lfq_in_limits(dim_g, d, Q)) return ALM_ERR_UNSUPPORTED;
-    const bool identity = !W_out && !b_out;
-    if (identity ? dim_g != d : (!W_out || !b_out)) return ALM_ERR_BAD_ARG;
+    bool identity, vec;
+    if (const int err = pq_check(idx && ldi >= ncols, M, dim_g, d, Q, LFQ_MAX_D, 1, ncols, Q, {{out, ldo}}, {W_out, b_out}, {W_out, b_out}, identity, vec))
+        return err;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((M + LFQ_ROWS - 1) / LFQ_ROWS));
+    const dim3 grid((unsigned)((M + PQ_ROWS - 1) / PQ_ROWS));
     if (identity) {
         hipLaunchKernelGGL(lfq_decode_identity_kernel, grid, dim3(256), 0, st, idx, ldi, out, ldo, M, d, ncols);
     } else {
-        const bool vec = dim_g % 4 == 0 && ldo % 4 == 0 && al16(out) && al16(W_out) && al16(b_out);
 #define ALM_CALL(N)                                                                                                             \
     if (vec) hipLaunchKernelGGL((lfq_decode_kernel<N, true>), grid, dim3(256), 0, st, idx, ldi, W_out, b_out, out, ldo, M, dim_g, ncols); \
     else hipLaunchKernelGGL((lfq_decode_kernel<N, false>), grid, dim3(256), 0, st, idx, ldi, W_out, b_out, out, ldo, M, dim_g, ncols)
@@ -707,11 +449,11 @@ extern "C" int alm_lfq_decode(const long long* idx, long long ldi, const float* 
 // until there are at most 1024 chunks) x the parameter gradients' 2 d dim_g + dim_g + d floats rounded up to 4 (none in the identity case
 // dim_g == d); -1 outside the limits or past 2^31
 extern "C" int alm_lfq_bwd_ws_floats(int M, int dim_g, int d, int Q) {
-    if (M <= 0 || dim_g <= 0 || d <= 0 || Q <= 0 || !lfq_in_limits(dim_g, d, Q)) return -1;
+    if (M <= 0 || dim_g <= 0 || d <= 0 || Q <= 0 || !pq_in_limits(dim_g, d, Q, LFQ_MAX_D)) return -1;
     long long n = up4((long long)Q * M * d);
     if (dim_g != d) {
-        const int ch = lfq_chunk(M);
-        n += (long long)((M + ch - 1) / ch) * lfq_epad(dim_g, d);
+        const int ch = pq_chunk(M);
+        n += (long long)((M + ch - 1) / ch) * pq_epad(dim_g, d);
     }
     return n > 0x7fffffffLL ? -1 : (int)n;
 }
@@ -720,14 +462,14 @@ extern "C" int alm_lfq_bwd(const float* g, long long ldg, const float* g_loss, c
                            const float* W_in, const float* W_out, float* dx, long long ldd, float* dW_in, float* db_in, float* dW_out, float* db_out,
                            float* ws, long long ws_floats, int M, int dim_g, int d, int Q, int k, float inv_temperature, float entropy_w, float commit_w,
                            float gamma, void* stream) {
-    if (M <= 0 || dim_g <= 0 || d <= 0 || Q <= 0 || k < 0 || k >= Q || !g || !x || !z || !dx || !ws || ldg < dim_g || ldx < dim_g || ldd < dim_g)
-        return ALM_ERR_BAD_ARG;
-    if (!lfq_in_limits(dim_g, d, Q)) return ALM_ERR_UNSUPPORTED;
+    bool identity, vec;                                            // ws stands for the partials: they start a multiple of 16 bytes behind it
+    if (const int err = pq_check(z && ws, M, dim_g, d, Q, LFQ_MAX_D, 0, k, Q - 1, {{g, ldg}, {x, ldx}, {dx, ldd}}, {W_in, W_out}, {W_in, W_out, ws},
+                                 identity, vec))
+        return err;
     if (g_loss && (!avg || !(inv_temperature > 0.f))) return ALM_ERR_BAD_ARG;
-    const bool identity = !W_in && !W_out;
-    if (identity ? dim_g != d : (!W_in || !W_out || !dW_in || !db_in || !dW_out || !db_out)) return ALM_ERR_BAD_ARG;
-    const int ch = lfq_chunk(M), NC = (M + ch - 1) / ch;
-    const long long n_gl = up4((long long)Q * M * d), epad = lfq_epad(dim_g, d), need = n_gl + (identity ? 0 : (long long)NC * epad);
+    if (!identity && (!dW_in || !db_in || !dW_out || !db_out)) return ALM_ERR_BAD_ARG;
+    const int ch = pq_chunk(M), NC = (M + ch - 1) / ch;
+    const long long n_gl = up4((long long)Q * M * d), epad = pq_epad(dim_g, d), need = n_gl + (identity ? 0 : (long long)NC * epad);
     if (need > 0x7fffffffLL) return ALM_ERR_UNSUPPORTED;
     if (ws_floats < need) return ALM_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -739,11 +481,10 @@ extern "C" int alm_lfq_bwd(const float* g, long long ldg, const float* g_loss, c
         ALM_LAUNCH_CHECK();
     }
     if (identity) {
-        hipLaunchKernelGGL(lfq_bwd_identity_kernel, dim3((unsigned)((M + LFQ_ROWS - 1) / LFQ_ROWS)), dim3(256), 0, st, g, ldg, gl, dx, ldd, M, d, k);
+        hipLaunchKernelGGL(lfq_bwd_identity_kernel, dim3((unsigned)((M + PQ_ROWS - 1) / PQ_ROWS)), dim3(256), 0, st, g, ldg, gl, dx, ldd, M, d, k);
         ALM_LAUNCH_CHECK();
         return 0;
     }
-    const bool vec = dim_g % 4 == 0 && ldg % 4 == 0 && ldx % 4 == 0 && ldd % 4 == 0 && al16(g) && al16(x) && al16(dx) && al16(W_in) && al16(W_out) && al16(part);
 #define ALM_CALL(N)                                                                                                                               \
     if (vec) hipLaunchKernelGGL((lfq_bwd_kernel<N, true>), dim3((unsigned)NC), dim3(256), 0, st, g, ldg, x, ldx, z, gl, W_in, W_out, dx, ldd,    \
                                 part, M, dim_g, k, ch, epad);                                                                                     \

@@ -81,15 +81,6 @@ struct MelPowerBwdOp {                                            // dP [F][Bh T
     }
 };
 
-__device__ __forceinline__ float block_sum(float v) {
-    __shared__ float part[4];
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
 // mel [2 Bh][n_mels][T]; frames [lo, hi) of this block, thread per frame; norms [Bh T]; part[blockIdx.x] = sum l1, part[RED_MAX_BLOCKS + blockIdx.x] = sum l2
 __global__ __launch_bounds__(256) void mel_frame_loss_kernel(const float* __restrict__ mel, float* __restrict__ norms, float* __restrict__ part, int Bh,
                                                              int n_mels, int T, int span) {

@@ -254,15 +254,6 @@ __global__ __launch_bounds__(256) void modrelu_fwd_kernel(const float2* __restri
     y[i] = o;
 }
 
-__device__ __forceinline__ float block_sum(float v) {
-    __shared__ float part[4];
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
 // dz elementwise; this block's share of db (a contiguous span, fixed lane order) into part[blockIdx.x]
 __global__ __launch_bounds__(256) void modrelu_bwd_kernel(const float2* __restrict__ g, const float2* __restrict__ z, const float* __restrict__ bp,
                                                           float2* __restrict__ dz, float* __restrict__ part, long long n, long long span) {

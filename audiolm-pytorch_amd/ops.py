@@ -1530,12 +1530,16 @@ def fsq_constants(levels, num_quantizers):
     return table
 
 
-def _fsq_args(mat, weights, consts, d, Q):
-    _chk(mat, F32), _chk(consts, F32)
+def _proj_quant_args(mat, weights, d, Q, consts=None):
+    """(M, dim_g, the four weights or four None) of one group's call of the FSQ / LFQ kernels; mat: its [M, dim_g] view; consts: FSQ's table"""
+    _chk(mat, F32)
+    if consts is not None:
+        _chk(consts, F32)
+        assert consts.is_contiguous() and consts.numel() == 56 + 16 * Q
     M, dim_g = mat.shape
-    assert mat.stride(1) == 1 and consts.is_contiguous() and consts.numel() == 56 + 16 * Q
+    assert mat.stride(1) == 1 and d >= 1 and Q >= 1
     if weights is None:
-        assert dim_g == d, 'the identity case needs dim_g == len(levels)'
+        assert dim_g == d, 'the identity case needs dim_g == the projected width'
         return M, dim_g, (None,) * 4
     w_in, b_in, w_out, b_out = weights
     for t in weights:
@@ -1548,7 +1552,7 @@ def _fsq_args(mat, weights, consts, d, Q):
 def fsq_fwd(x, weights, consts, d, Q, k, idx_out, out, save_z=False):
     """x [M, dim_g] view -> idx_out int64 [M, Q] view (-1 past layer k) and out [M, dim_g] view, both written in place; returns z float64 [M, d] (the
     projected input in the precision the chain runs in, what fsq_bwd needs) with save_z, else None (alm_fsq_fwd)"""
-    M, dim_g, (w_in, b_in, w_out, b_out) = _fsq_args(x, weights, consts, d, Q)
+    M, dim_g, (w_in, b_in, w_out, b_out) = _proj_quant_args(x, weights, d, Q, consts)
     _chk(out, F32), _chk(idx_out, torch.int64)
     assert tuple(out.shape) == (M, dim_g) and out.stride(1) == 1 and tuple(idx_out.shape) == (M, Q) and idx_out.stride(1) == 1
     z = _new((M, d), dtype=torch.float64, device=x.device) if save_z else None
@@ -1559,7 +1563,7 @@ def fsq_fwd(x, weights, consts, d, Q, k, idx_out, out, save_z=False):
 
 def fsq_decode(idx, weights, consts, d, Q, out):
     """idx int64 [M, q <= Q] view (negative = no code) -> out [M, dim_g] view, written in place (alm_fsq_decode)"""
-    M, dim_g, (_, _, w_out, b_out) = _fsq_args(out, weights, consts, d, Q)
+    M, dim_g, (_, _, w_out, b_out) = _proj_quant_args(out, weights, d, Q, consts)
     _chk(idx, torch.int64)
     assert idx.dim() == 2 and idx.shape[0] == M and 1 <= idx.shape[1] <= Q and idx.stride(1) == 1
     _lib.call('alm_fsq_decode', idx.data_ptr(), idx.stride(0), _p(w_out), _p(b_out), consts.data_ptr(), out.data_ptr(), out.stride(0), M, dim_g, d, Q,
@@ -1571,7 +1575,7 @@ def fsq_bwd(g, x, z, weights, consts, d, Q, k, dx):
     """g = dL/dout, x [M, dim_g] views, z [M, d] from fsq_fwd (None in the identity case) -> dx view written in place; returns (dW_in, db_in, dW_out,
     db_out), or () in the identity case.  The parameter gradients are per-row-chunk partials in a workspace of alm_fsq_bwd_ws_floats floats, added in
     chunk order by a second launch."""
-    M, dim_g, (w_in, _, w_out, _) = _fsq_args(x, weights, consts, d, Q)
+    M, dim_g, (w_in, _, w_out, _) = _proj_quant_args(x, weights, d, Q, consts)
     _chk(g, F32), _chk(dx, F32)
     assert tuple(g.shape) == (M, dim_g) and g.stride(1) == 1 and tuple(dx.shape) == (M, dim_g) and dx.stride(1) == 1
     grads, ws, n = (), None, 0
@@ -1596,26 +1600,11 @@ LFQ_MAX_CODEBOOK_BITS, LFQ_MAX_DIM, LFQ_MAX_QUANTIZERS = 10, 1024, 32
 LFQ_INV_TEMPERATURE = 100.             # the package's default; not a constructor argument of the reference
 
 
-def _lfq_args(mat, weights, d, Q):
-    _chk(mat, F32)
-    M, dim_g = mat.shape
-    assert mat.stride(1) == 1 and d >= 1 and Q >= 1
-    if weights is None:
-        assert dim_g == d, 'the identity case needs dim_g == log2(codebook_size)'
-        return M, dim_g, (None,) * 4
-    w_in, b_in, w_out, b_out = weights
-    for t in weights:
-        _chk(t, F32)
-        assert t.is_contiguous()
-    assert tuple(w_in.shape) == (d, dim_g) and tuple(b_in.shape) == (d,) and tuple(w_out.shape) == (dim_g, d) and tuple(b_out.shape) == (dim_g,)
-    return M, dim_g, tuple(weights)
-
-
 def lfq_fwd(x, weights, d, Q, k, idx_out, out, loss_cfg=None, ws=None):
     """x [M, dim_g] view -> idx_out int64 [M, Q] view (-1 past layer k) and out [M, dim_g] view, both written in place.  With loss_cfg (training
     mode) returns (z float64 [M, d], losses fp32 [Q] (0 past k), avg float64 [Q, 2^d] = the mean code distribution per layer: what lfq_bwd needs),
     else (None, None, None).  ws: a float64 workspace of at least alm_lfq_fwd_ws_doubles elements (allocated when None)  (alm_lfq_fwd)"""
-    M, dim_g, (w_in, b_in, w_out, b_out) = _lfq_args(x, weights, d, Q)
+    M, dim_g, (w_in, b_in, w_out, b_out) = _proj_quant_args(x, weights, d, Q)
     _chk(out, F32), _chk(idx_out, torch.int64)
     assert tuple(out.shape) == (M, dim_g) and out.stride(1) == 1 and tuple(idx_out.shape) == (M, Q) and idx_out.stride(1) == 1
     z = losses = avg = None
@@ -1640,7 +1629,7 @@ def lfq_fwd(x, weights, d, Q, k, idx_out, out, loss_cfg=None, ws=None):
 
 def lfq_decode(idx, weights, d, Q, out):
     """idx int64 [M, q <= Q] view (negative = no code) -> out [M, dim_g] view, written in place (alm_lfq_decode)"""
-    M, dim_g, (_, _, w_out, b_out) = _lfq_args(out, weights, d, Q)
+    M, dim_g, (_, _, w_out, b_out) = _proj_quant_args(out, weights, d, Q)
     _chk(idx, torch.int64)
     assert idx.dim() == 2 and idx.shape[0] == M and 1 <= idx.shape[1] <= Q and idx.stride(1) == 1
     _lib.call('alm_lfq_decode', idx.data_ptr(), idx.stride(0), _p(w_out), _p(b_out), out.data_ptr(), out.stride(0), M, dim_g, d, Q, idx.shape[1], _st())
@@ -1650,7 +1639,7 @@ def lfq_decode(idx, weights, d, Q, out):
 def lfq_bwd(g, g_loss, x, z, avg, weights, d, Q, k, dx, loss_cfg, ws=None):
     """g = dL/dout [M, dim_g] view, g_loss = dL/dlosses fp32 [Q] or None, x view, (z, avg) from lfq_fwd -> dx view written in place; returns (dW_in,
     db_in, dW_out, db_out), or () in the identity case.  ws: an fp32 workspace of at least alm_lfq_bwd_ws_floats elements (allocated when None)"""
-    M, dim_g, (w_in, _, w_out, _) = _lfq_args(x, weights, d, Q)
+    M, dim_g, (w_in, _, w_out, _) = _proj_quant_args(x, weights, d, Q)
     _chk(g, F32), _chk(dx, F32), _chk(z, torch.float64)
     assert tuple(g.shape) == (M, dim_g) and g.stride(1) == 1 and tuple(dx.shape) == (M, dim_g) and dx.stride(1) == 1
     assert z.is_contiguous() and tuple(z.shape) == (M, d)

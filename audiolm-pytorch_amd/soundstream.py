@@ -485,90 +485,57 @@ class GroupedResidualVQ(nn.Module):
         return out.view(b, n, self.dim)
 
 
-class _ResidualFSQ(nn.Module):
-    def __init__(self, dim, codebook_dim):
+class _GroupedProjQuant(nn.Module):
+    """What GroupedResidualFSQ and GroupedResidualLFQ share (csrc/proj_quant.hpp is the kernels' side of it): per group a projection to `proj_dim`
+    dimensions, Q layers of a per-dimension residual chain, a projection back.  rvqs.{g}.project_in / project_out are nn.Linear, or nn.Identity when
+    dim / groups == proj_dim.  Quantize dropout (training mode only) is GroupedResidualVQ.dropout_index.  A subclass builds `rvqs` and supplies
+    `run` and `decode_group`, its per-group kernel calls."""
+
+    def __init__(self, *, dim, groups, num_quantizers, proj_dim, proj_dim_name, limits, quantize_dropout, quantize_dropout_cutoff_index,
+                 quantize_dropout_multiple_of):
         super().__init__()
-        self.project_in = nn.Linear(dim, codebook_dim) if dim != codebook_dim else nn.Identity()
-        self.project_out = nn.Linear(codebook_dim, dim) if dim != codebook_dim else nn.Identity()
-
-
-class GroupedResidualFSQ(nn.Module):
-    """Residual finite scalar quantization (arXiv 2309.15505) in the grouped form of vector-quantize-pytorch's GroupedResidualFSQ, as the reference
-    builds it (soundstream.py:578-586).  The arithmetic is RESTATED from the paper's Appendix A and the package's residual form (tests/fsq_restated.py;
-    parity with the installed package is unpinned, like LocalMHA): per group a projection to len(levels) dimensions, Q layers of bounded rounding of
-    the scaled residual, a projection back.  No codebook state, no auxiliary loss: one alm_fsq_fwd launch per group, alm_fsq_decode for
-    `get_output_from_indices`, and in training mode with a graph wanted codec_bwd.FsqFn (alm_fsq_bwd).  rvqs.{g}.project_in / project_out are
-    nn.Linear, or nn.Identity when dim / groups == len(levels).  Quantize dropout (training mode only) is GroupedResidualVQ.dropout_index."""
-
-    def __init__(self, *, dim, levels, num_quantizers, groups=1, quantize_dropout=True, quantize_dropout_cutoff_index=1, quantize_dropout_multiple_of=1):
-        super().__init__()
-        levels = [int(l) for l in levels]
-        assert dim % groups == 0 and num_quantizers >= 1 and len(levels) >= 1 and all(l >= 2 for l in levels)
+        assert dim % groups == 0 and num_quantizers >= 1
         assert quantize_dropout_cutoff_index >= 0 and quantize_dropout_multiple_of >= 1
-        dg = dim // groups
-        if len(levels) > ops.FSQ_MAX_LEVELS:
-            raise NotImplementedError(f'GroupedResidualFSQ: len(levels) = {len(levels)} exceeds the kernels\' limit of {ops.FSQ_MAX_LEVELS}')
-        if dg > ops.FSQ_MAX_DIM:
-            raise NotImplementedError(f'GroupedResidualFSQ: dim / groups = {dg} exceeds the kernels\' limit of {ops.FSQ_MAX_DIM}')
-        if num_quantizers > ops.FSQ_MAX_QUANTIZERS:
-            raise NotImplementedError(f'GroupedResidualFSQ: num_quantizers = {num_quantizers} exceeds the kernels\' limit of {ops.FSQ_MAX_QUANTIZERS}')
-        self.codebook_size = functools.reduce(lambda a, b: a * b, levels)
-        if self.codebook_size > 1 << 24:
-            raise NotImplementedError(f'GroupedResidualFSQ: codebook_size = prod(levels) = {self.codebook_size} exceeds 2^24 (the index basis is fp32)')
-        self.dim, self.levels, self.groups, self.num_quantizers = dim, levels, groups, num_quantizers
+        for what, v, limit in zip((proj_dim_name, 'dim / groups', 'num_quantizers'), (proj_dim, dim // groups, num_quantizers), limits):
+            if v > limit:
+                raise NotImplementedError(f'{type(self).__name__}: {what} = {v} exceeds the kernels\' limit of {limit}')
+        self.dim, self.groups, self.num_quantizers, self.proj_dim = dim, groups, num_quantizers, proj_dim
         self.quantize_dropout = quantize_dropout and num_quantizers > 1
         self.quantize_dropout_cutoff_index, self.quantize_dropout_multiple_of = quantize_dropout_cutoff_index, quantize_dropout_multiple_of
-        self.rvqs = nn.ModuleList([_ResidualFSQ(dg, len(levels)) for _ in range(groups)])
-        self.constants = ops.fsq_constants(levels, num_quantizers)           # host table (fp32, CPU); a plain attribute: the state_dict has no entry for it
-        self._constants_on = {}
 
     dropout_index = GroupedResidualVQ.dropout_index
-
-    def _consts(self, device):
-        if device not in self._constants_on:
-            self._constants_on[device] = self.constants.to(device)
-        return self._constants_on[device]
 
     def group_params(self, g):
         """[project_in.weight, project_in.bias, project_out.weight, project_out.bias] of group g, or [] in the identity case"""
         r = self.rvqs[g]
         return [] if isinstance(r.project_in, nn.Identity) else [r.project_in.weight, r.project_in.bias, r.project_out.weight, r.project_out.bias]
 
+    def all_params(self):
+        return [p for g in range(self.groups) for p in self.group_params(g)]
+
     @staticmethod
     def kernel_weights(params):
         return tuple(p.detach().to(F32).contiguous() for p in params) if params else None
 
-    def run(self, x2, k, save_z=False):
-        """x2 fp32 [M, dim], k = last active layer -> (out [M, dim], idx int64 [g, M, Q] (-1 past k), per group z [M, d] or None)"""
+    def groups_of(self, x2):
+        """x2 fp32 [M, dim] -> (out [M, dim], idx int64 [g, M, Q], per group (its columns, its kernel weights)): what `run` fills"""
         M, dim = x2.shape
-        dg, d, Q = dim // self.groups, len(self.levels), self.num_quantizers
+        dg = dim // self.groups
         out = torch.empty((M, dim), dtype=F32, device=x2.device)
-        idx = torch.empty((self.groups, M, Q), dtype=torch.int64, device=x2.device)
-        consts = self._consts(x2.device)
-        zs = []
-        for g in range(self.groups):
-            weights = self.kernel_weights(self.group_params(g))
-            zs.append(ops.fsq_fwd(x2[:, g * dg:(g + 1) * dg], weights, consts, d, Q, k, idx[g], out[:, g * dg:(g + 1) * dg],
-                                  save_z=save_z and weights is not None))
-        return out, idx, zs
+        idx = torch.empty((self.groups, M, self.num_quantizers), dtype=torch.int64, device=x2.device)
+        return out, idx, [(slice(g * dg, (g + 1) * dg), self.kernel_weights(self.group_params(g))) for g in range(self.groups)]
 
-    def forward(self, x):
-        """x fp32 (b, n, dim) -> (quantized (b, n, dim), indices (g, b, n, q) int64; -1 on the layers quantize dropout left out)"""
+    def flatten(self, x):
+        """x (b, n, dim) -> (x2 fp32 [b n, dim], k = the last active layer of this call)"""
         if not x.is_cuda:
             raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
         b, n, dim = x.shape
         assert dim == self.dim
-        x2 = x.reshape(b * n, dim).to(F32).contiguous()
-        k = self.dropout_index() if self.training else self.num_quantizers - 1
-        if codec_bwd.wants_grad(self, x2):
-            out, idx = codec_bwd.FsqFn.apply(x2, self, k, *[p for g in range(self.groups) for p in self.group_params(g)])
-        else:
-            out, idx, _ = self.run(x2.detach(), k)
-        return out.view(b, n, dim), idx.view(self.groups, b, n, self.num_quantizers)
+        return x.reshape(b * n, dim).to(F32).contiguous(), self.dropout_index() if self.training else self.num_quantizers - 1
 
     @torch.no_grad()
     def get_output_from_indices(self, indices):
-        """indices int (g, b, n, q <= Q) (-1 = no code) -> (b, n, dim): per group project_out of the summed codes (alm_fsq_decode)"""
+        """indices int (g, b, n, q <= Q) (-1 = no code) -> (b, n, dim): per group project_out of the summed codes (alm_fsq_decode / alm_lfq_decode)"""
         g, b, n, q = indices.shape
         assert g == self.groups and 1 <= q <= self.num_quantizers
         if not indices.is_cuda:
@@ -576,10 +543,63 @@ class GroupedResidualFSQ(nn.Module):
         dg = self.dim // self.groups
         out = torch.empty((b * n, self.dim), dtype=F32, device=indices.device)
         idx = indices.to(torch.int64).reshape(g, b * n, q).contiguous()
-        consts = self._consts(indices.device)
         for gi in range(g):
-            ops.fsq_decode(idx[gi], self.kernel_weights(self.group_params(gi)), consts, len(self.levels), self.num_quantizers, out[:, gi * dg:(gi + 1) * dg])
+            self.decode_group(idx[gi], self.kernel_weights(self.group_params(gi)), out[:, gi * dg:(gi + 1) * dg])
         return out.view(b, n, self.dim)
+
+
+class _ResidualFSQ(nn.Module):
+    def __init__(self, dim, codebook_dim):
+        super().__init__()
+        self.project_in = nn.Linear(dim, codebook_dim) if dim != codebook_dim else nn.Identity()
+        self.project_out = nn.Linear(codebook_dim, dim) if dim != codebook_dim else nn.Identity()
+
+
+class GroupedResidualFSQ(_GroupedProjQuant):
+    """Residual finite scalar quantization (arXiv 2309.15505) in the grouped form of vector-quantize-pytorch's GroupedResidualFSQ, as the reference
+    builds it (soundstream.py:578-586).  The arithmetic is RESTATED from the paper's Appendix A and the package's residual form (tests/fsq_restated.py;
+    parity with the installed package is unpinned, like LocalMHA): per group a projection to len(levels) dimensions, Q layers of bounded rounding of
+    the scaled residual, a projection back.  No codebook state, no auxiliary loss: one alm_fsq_fwd launch per group, alm_fsq_decode for
+    `get_output_from_indices`, and in training mode with a graph wanted codec_bwd.FsqFn (alm_fsq_bwd)."""
+
+    def __init__(self, *, dim, levels, num_quantizers, groups=1, quantize_dropout=True, quantize_dropout_cutoff_index=1, quantize_dropout_multiple_of=1):
+        levels = [int(l) for l in levels]
+        assert len(levels) >= 1 and all(l >= 2 for l in levels)
+        super().__init__(dim=dim, groups=groups, num_quantizers=num_quantizers, proj_dim=len(levels), proj_dim_name='len(levels)',
+                         limits=(ops.FSQ_MAX_LEVELS, ops.FSQ_MAX_DIM, ops.FSQ_MAX_QUANTIZERS), quantize_dropout=quantize_dropout,
+                         quantize_dropout_cutoff_index=quantize_dropout_cutoff_index, quantize_dropout_multiple_of=quantize_dropout_multiple_of)
+        self.codebook_size = functools.reduce(lambda a, b: a * b, levels)
+        if self.codebook_size > 1 << 24:
+            raise NotImplementedError(f'GroupedResidualFSQ: codebook_size = prod(levels) = {self.codebook_size} exceeds 2^24 (the index basis is fp32)')
+        self.levels = levels
+        self.rvqs = nn.ModuleList([_ResidualFSQ(dim // groups, len(levels)) for _ in range(groups)])
+        self.constants = ops.fsq_constants(levels, num_quantizers)           # host table (fp32, CPU); a plain attribute: the state_dict has no entry for it
+        self._constants_on = {}
+
+    def _consts(self, device):
+        if device not in self._constants_on:
+            self._constants_on[device] = self.constants.to(device)
+        return self._constants_on[device]
+
+    def run(self, x2, k, save_z=False):
+        """x2 fp32 [M, dim], k = last active layer -> (out [M, dim], idx int64 [g, M, Q] (-1 past k), per group z [M, d] or None)"""
+        out, idx, groups = self.groups_of(x2)
+        consts = self._consts(x2.device)
+        zs = [ops.fsq_fwd(x2[:, sl], weights, consts, self.proj_dim, self.num_quantizers, k, idx[g], out[:, sl], save_z=save_z and weights is not None)
+              for g, (sl, weights) in enumerate(groups)]
+        return out, idx, zs
+
+    def forward(self, x):
+        """x fp32 (b, n, dim) -> (quantized (b, n, dim), indices (g, b, n, q) int64; -1 on the layers quantize dropout left out)"""
+        x2, k = self.flatten(x)
+        if codec_bwd.wants_grad(self, x2):
+            out, idx = codec_bwd.FsqFn.apply(x2, self, k, *self.all_params())
+        else:
+            out, idx, _ = self.run(x2.detach(), k)
+        return out.view(x.shape), idx.view(self.groups, *x.shape[:2], self.num_quantizers)
+
+    def decode_group(self, idx, weights, out):
+        ops.fsq_decode(idx, weights, self._consts(idx.device), self.proj_dim, self.num_quantizers, out)
 
 
 class _LFQLayer(nn.Module):
@@ -596,97 +616,60 @@ class _ResidualLFQ(nn.Module):
         self.layers = nn.ModuleList([_LFQLayer(codebook_bits) for _ in range(num_quantizers)])
 
 
-class GroupedResidualLFQ(nn.Module):
+class GroupedResidualLFQ(_GroupedProjQuant):
     """Residual lookup-free quantization (arXiv 2310.05737) in the grouped form of vector-quantize-pytorch's GroupedResidualLFQ, as the reference
     builds it (soundstream.py:563-571).  The arithmetic is RESTATED from the paper and the package's residual form (tests/lfq_restated.py; parity with
     the installed package is unpinned, like FSQ and LocalMHA): per group a projection to d = log2(codebook_size) dimensions, Q layers of sign
     quantization of the residual at scale 2^-q, a projection back.  No codebook state; in training mode every active layer carries the entropy loss
     (per-sample entropy minus diversity_gamma times the entropy of the batch's mean code distribution, over all 2^d codes) and the optional
     commitment loss: alm_lfq_fwd per group, alm_lfq_decode for `get_output_from_indices`, and with a graph wanted codec_bwd.LfqFn (alm_lfq_bwd).
-    rvqs.{g}.project_in / project_out are nn.Linear, or nn.Identity when dim / groups == d; rvqs.{g}.layers.{q}.mask is the package's per-layer
-    buffer (2^(d-1) .. 1, int64).  Quantize dropout (training mode only) is GroupedResidualVQ.dropout_index."""
+    rvqs.{g}.layers.{q}.mask is the package's per-layer buffer (2^(d-1) .. 1, int64)."""
 
     def __init__(self, *, dim, num_quantizers, codebook_size, groups=1, quantize_dropout=True, quantize_dropout_cutoff_index=1,
                  quantize_dropout_multiple_of=1, entropy_loss_weight=0.1, commitment_loss_weight=0., diversity_gamma=1.):
-        super().__init__()
         codebook_size = int(codebook_size)
-        assert dim % groups == 0 and num_quantizers >= 1
         assert codebook_size >= 2 and codebook_size & (codebook_size - 1) == 0, f'codebook_size = {codebook_size} must be a power of two >= 2'
-        assert quantize_dropout_cutoff_index >= 0 and quantize_dropout_multiple_of >= 1
-        d, dg = codebook_size.bit_length() - 1, dim // groups
-        if d > ops.LFQ_MAX_CODEBOOK_BITS:
-            raise NotImplementedError(f'GroupedResidualLFQ: log2(codebook_size) = {d} exceeds the kernels\' limit of {ops.LFQ_MAX_CODEBOOK_BITS}')
-        if dg > ops.LFQ_MAX_DIM:
-            raise NotImplementedError(f'GroupedResidualLFQ: dim / groups = {dg} exceeds the kernels\' limit of {ops.LFQ_MAX_DIM}')
-        if num_quantizers > ops.LFQ_MAX_QUANTIZERS:
-            raise NotImplementedError(f'GroupedResidualLFQ: num_quantizers = {num_quantizers} exceeds the kernels\' limit of {ops.LFQ_MAX_QUANTIZERS}')
-        self.dim, self.codebook_size, self.codebook_bits, self.groups, self.num_quantizers = dim, codebook_size, d, groups, num_quantizers
-        self.quantize_dropout = quantize_dropout and num_quantizers > 1
-        self.quantize_dropout_cutoff_index, self.quantize_dropout_multiple_of = quantize_dropout_cutoff_index, quantize_dropout_multiple_of
+        d = codebook_size.bit_length() - 1
+        super().__init__(dim=dim, groups=groups, num_quantizers=num_quantizers, proj_dim=d, proj_dim_name='log2(codebook_size)',
+                         limits=(ops.LFQ_MAX_CODEBOOK_BITS, ops.LFQ_MAX_DIM, ops.LFQ_MAX_QUANTIZERS), quantize_dropout=quantize_dropout,
+                         quantize_dropout_cutoff_index=quantize_dropout_cutoff_index, quantize_dropout_multiple_of=quantize_dropout_multiple_of)
+        self.codebook_size, self.codebook_bits = codebook_size, d
         self.entropy_loss_weight, self.commitment_loss_weight, self.diversity_gamma = float(entropy_loss_weight), float(commitment_loss_weight), float(diversity_gamma)
         self.inv_temperature = ops.LFQ_INV_TEMPERATURE
-        self.rvqs = nn.ModuleList([_ResidualLFQ(dg, d, num_quantizers) for _ in range(groups)])
-
-    dropout_index = GroupedResidualVQ.dropout_index
-    kernel_weights = staticmethod(GroupedResidualFSQ.kernel_weights)
+        self.rvqs = nn.ModuleList([_ResidualLFQ(dim // groups, d, num_quantizers) for _ in range(groups)])
 
     @property
     def loss_cfg(self):
         return (self.inv_temperature, self.entropy_loss_weight, self.commitment_loss_weight, self.diversity_gamma)
 
-    def group_params(self, g):
-        """[project_in.weight, project_in.bias, project_out.weight, project_out.bias] of group g, or [] in the identity case"""
-        r = self.rvqs[g]
-        return [] if isinstance(r.project_in, nn.Identity) else [r.project_in.weight, r.project_in.bias, r.project_out.weight, r.project_out.bias]
-
     def run(self, x2, k, with_losses=False):
         """x2 fp32 [M, dim], k = last active layer -> (out [M, dim], idx int64 [g, M, Q] (-1 past k), losses [g, Q] (zeros without with_losses),
         per group (z [M, d] float64, avg [Q, 2^d] float64) or None)"""
-        M, dim = x2.shape
-        dg, d, Q = dim // self.groups, self.codebook_bits, self.num_quantizers
-        out = torch.empty((M, dim), dtype=F32, device=x2.device)
-        idx = torch.empty((self.groups, M, Q), dtype=torch.int64, device=x2.device)
+        out, idx, groups = self.groups_of(x2)
         losses, saved = [], []
-        for g in range(self.groups):
-            weights = self.kernel_weights(self.group_params(g))
-            z, l, avg = ops.lfq_fwd(x2[:, g * dg:(g + 1) * dg], weights, d, Q, k, idx[g], out[:, g * dg:(g + 1) * dg],
+        for g, (sl, weights) in enumerate(groups):
+            z, l, avg = ops.lfq_fwd(x2[:, sl], weights, self.proj_dim, self.num_quantizers, k, idx[g], out[:, sl],
                                     loss_cfg=self.loss_cfg if with_losses else None)
             losses.append(l)
             saved.append((z, avg) if with_losses else None)
-        losses = torch.stack(losses) if with_losses else torch.zeros((self.groups, Q), dtype=F32, device=x2.device)
+        losses = torch.stack(losses) if with_losses else torch.zeros((self.groups, self.num_quantizers), dtype=F32, device=x2.device)
         return out, idx, losses, saved
 
     def forward(self, x):
         """x fp32 (b, n, dim) -> (quantized (b, n, dim), indices (g, b, n, q) int64; -1 on the layers quantize dropout left out, losses (g, q):
         zeros in eval mode and on the layers left out)"""
-        if not x.is_cuda:
-            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
-        if self.training and torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        if x.is_cuda and self.training and torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise NotImplementedError('train-mode GroupedResidualLFQ is single-process: the all-reduce of the mean code distribution (the diversity '
                                       'term of the entropy loss) is not implemented')
-        b, n, dim = x.shape
-        assert dim == self.dim
-        x2 = x.reshape(b * n, dim).to(F32).contiguous()
-        k = self.dropout_index() if self.training else self.num_quantizers - 1
+        x2, k = self.flatten(x)
         if self.training and codec_bwd.wants_grad(self, x2):
-            out, idx, losses = codec_bwd.LfqFn.apply(x2, self, k, *[p for g in range(self.groups) for p in self.group_params(g)])
+            out, idx, losses = codec_bwd.LfqFn.apply(x2, self, k, *self.all_params())
         else:
             out, idx, losses, _ = self.run(x2.detach(), k, with_losses=self.training)
-        return out.view(b, n, dim), idx.view(self.groups, b, n, self.num_quantizers), losses
+        return out.view(x.shape), idx.view(self.groups, *x.shape[:2], self.num_quantizers), losses
 
-    @torch.no_grad()
-    def get_output_from_indices(self, indices):
-        """indices int (g, b, n, q <= Q) (-1 = no code) -> (b, n, dim): per group project_out of the summed codes (alm_lfq_decode)"""
-        g, b, n, q = indices.shape
-        assert g == self.groups and 1 <= q <= self.num_quantizers
-        if not indices.is_cuda:
-            raise RuntimeError('audiolm_pytorch_amd.SoundStream runs on the MI355X only (no CPU fallback)')
-        dg = self.dim // self.groups
-        out = torch.empty((b * n, self.dim), dtype=F32, device=indices.device)
-        idx = indices.to(torch.int64).reshape(g, b * n, q).contiguous()
-        for gi in range(g):
-            ops.lfq_decode(idx[gi], self.kernel_weights(self.group_params(gi)), self.codebook_bits, self.num_quantizers, out[:, gi * dg:(gi + 1) * dg])
-        return out.view(b, n, self.dim)
+    def decode_group(self, idx, weights, out):
+        ops.lfq_decode(idx, weights, self.proj_dim, self.num_quantizers, out)
 
 
 # ---------------------------------------------------------------------------------------------- LocalTransformer (soundstream.py:397-440)

@@ -72,6 +72,9 @@ KERNEL_CASES = [
     (257, 1024, (8, 8, 8, 5, 5, 5), 4, 3, 8),
     (130, 4, (8, 5, 5, 5), 2, 1, 2),
     (45, 30, (8, 5, 5, 5), 3, 2, 0),
+    (67, 40, (4, 3, 3, 3, 3, 2, 2, 2), 2, 1, 5),       # d = 8: the LDS row stride equals d
+    (50, 36, (5, 5, 5, 4, 4, 3, 3), 3, 2, 0),          # d = 7
+    (33, 258, (8, 5, 5, 5), 3, 2, 0),                  # scalar accesses, two column passes, a ragged last piece
 ]
 
 

@@ -79,6 +79,10 @@ KERNEL_CASES = [
     (45, 30, 256, 3, 2, 0),
     (257, 128, 2, 2, 1, 0),
     (209, 64, 1024, 8, 7, 0),
+    (67, 40, 128, 2, 1, 0),                            # d = 7
+    (50, 36, 512, 3, 2, 0),                            # d = 9
+    (41, 20, 8, 2, 1, 0),                              # d = 3
+    (33, 258, 64, 3, 2, 0),                            # d = 6, scalar accesses, two column passes
 ]
 COMMIT_WEIGHTS = (0., 0.25)
 MODES = ('g_out', 'g_loss', 'both')
