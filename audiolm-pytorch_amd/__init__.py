@@ -2,7 +2,7 @@
 
 The directory is called `audiolm-pytorch_amd/` (repo contract); import it as `audiolm_pytorch_amd` through the loader module
 `audiolm_pytorch_amd.py` at the repo root.  `install_as_reference()` additionally registers these modules under the reference's
-import paths (`audiolm_pytorch.audiolm_pytorch`, `.attend`, `.soundstream`, `.encodec`, `.t5`) so that an unmodified reference trainer.py picks
+import paths (`audiolm_pytorch.audiolm_pytorch`, `.attend`, `.soundstream`, `.encodec`, `.t5`, `.hubert_kmeans`, `.vq_wav2vec`) so that an unmodified reference trainer.py picks
 them up.
 """
 from __future__ import annotations
@@ -23,9 +23,10 @@ from .hubert_kmeans import HubertWithKmeans
 from .mel_loss import MelSpectrogram, multi_spectral_recon_loss
 from .optimizer import FusedAdam, get_optimizer
 from .resample import resample
-from .soundstream import SoundStream
+from .soundstream import AudioLMSoundStream, MusicLMSoundStream, SoundStream
 from .t5 import T5Encoder, load_t5, register_t5, t5_encode_text
 from .version import __version__
+from .vq_wav2vec import FairseqVQWav2Vec
 
 
 def install_as_reference():
@@ -45,11 +46,15 @@ def install_as_reference():
         from . import soundstream
         sys.modules['audiolm_pytorch.soundstream'] = soundstream
         pkg.SoundStream = soundstream.SoundStream
+        pkg.AudioLMSoundStream, pkg.MusicLMSoundStream = soundstream.AudioLMSoundStream, soundstream.MusicLMSoundStream
     except ImportError:
         pass
     from . import hubert_kmeans
     sys.modules['audiolm_pytorch.hubert_kmeans'] = hubert_kmeans
     pkg.HubertWithKmeans = hubert_kmeans.HubertWithKmeans
+    from . import vq_wav2vec
+    sys.modules['audiolm_pytorch.vq_wav2vec'] = vq_wav2vec
+    pkg.FairseqVQWav2Vec = vq_wav2vec.FairseqVQWav2Vec
     from . import encodec
     sys.modules['audiolm_pytorch.encodec'] = encodec              # trainer.py:37 `from audiolm_pytorch.encodec import EncodecWrapper`
     pkg.EncodecWrapper = encodec.EncodecWrapper

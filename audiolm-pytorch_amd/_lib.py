@@ -142,7 +142,13 @@ SIGNATURES = {
     'alm_conv1d_valid': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'alm_layernorm_bct_split': [_P, _P, _P, _P, _I, _I, _I, _F, _P],
     'alm_mha_attn_fwd': [_P, _P, _I, _I, _I, _I, _F, _P],
-    'alm_t5_embed': [_P, _P, _P, _I, _I, _L, _P, _P],
+    'alm_vqw2v_group_chunks': [_I, _I, _I],
+    'alm_vqw2v_group_stats': [_P, _P, _P, _I, _I, _I, _I, _F, _P],
+    'alm_vqw2v_group_apply': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],
+    'alm_vqw2v_group_apply_t': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    'alm_vqw2v_conv0_stats': [_P, _L, _P, _P, _P, _I, _I, _L, _L, _I, _I, _F, _P],
+    'alm_vqw2v_conv0_apply': [_P, _L, _P, _P, _P, _P, _P, _I, _I, _L, _L, _I, _I, _I, _P],
+    'alm_t5_embed':[_P, _P, _P, _I, _I, _L, _P, _P],
     'alm_t5_rmsnorm': [_P, _P, _P, _P, _I, _I, _F, _I, _P],
     'alm_t5_gate': [_P, _P, _L, _L, _I, _P],
     'alm_t5_attn_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _P],

@@ -19,7 +19,7 @@ STAMP = os.path.join(HERE, '.libaudiolm_hip.stamp')
 SOURCES = ['gemm.hip', 'norm_act.hip', 'attention.hip', 'hyper.hip', 'embed_ce.hip', 'codec.hip', 'relpos.hip', 'optim.hip', 'decode.hip',
            'xattn.hip', 'local_attn.hip', 'launchlist.hip', 'resample.hip', 'dense_f32.hip', 'hubert.hip', 't5.hip',
            'encodec.hip', 'codec_bwd.hip', 'local_attn_bwd.hip', 'rvq_train.hip', 'discr.hip', 'stft_discr.hip', 'mel_loss.hip',
-           'film_se.hip', 'fsq.hip', 'lfq.hip', 'gate_loop.hip']
+           'film_se.hip', 'fsq.hip', 'lfq.hip', 'gate_loop.hip', 'vq_wav2vec.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value']
 
 

@@ -1,4 +1,4 @@
-"""What the frozen, inference-only fp32 models (HubertWithKmeans, T5Encoder, EncodecWrapper) share on the host: a parameter tree registered under the
+"""What the frozen, inference-only fp32 models (HubertWithKmeans, FairseqVQWav2Vec, T5Encoder, EncodecWrapper) share on the host: a parameter tree registered under the
 checkpoint's own key names, the key checks, and one cache of derived tensors."""
 from __future__ import annotations
 

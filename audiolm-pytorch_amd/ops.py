@@ -1805,6 +1805,86 @@ def mha_attn(qkv, heads, scale=None, dim_head=64):
     return out
 
 
+# ---- vq-wav2vec (csrc/vq_wav2vec.hip): GroupNorm over whole (C / G) x T blocks, fp32 [B, C, T], no atomics ----
+def vqw2v_group_stats(x, groups, eps=1e-5):
+    """x fp32 [B, C, T] contiguous -> stats fp32 [B, groups, 2] = (mean, rstd) of nn.GroupNorm(groups, C) (alm_vqw2v_group_stats: centred sums per
+    chunk of 4096 elements, the chunks merged in a fixed order in fp64)"""
+    _chk(x, F32)
+    assert x.dim() == 3 and x.is_contiguous()
+    B, C, T = x.shape
+    chunks = _lib.query('alm_vqw2v_group_chunks', C, T, groups)
+    if chunks < 0:
+        raise _lib.AlmError(f'vqw2v_group_stats: {groups} groups do not divide {C} channels, or C T = {C * T} does not fit 32 bits')
+    part = _new((B, groups, chunks, 2), dtype=F32, device=x.device)
+    stats = _new((B, groups, 2), dtype=F32, device=x.device)
+    _lib.call('alm_vqw2v_group_stats', x.data_ptr(), part.data_ptr(), stats.data_ptr(), B, C, T, groups, float(eps), _st())
+    return stats
+
+
+def _affine(x, stats, gamma, beta):
+    B, C, T = x.shape
+    _chk(x, F32), _chk(stats, F32), _chk(gamma, F32), _chk(beta, F32)
+    assert x.is_contiguous() and stats.is_contiguous() and stats.dim() == 3 and stats.shape[0] == B and stats.shape[2] == 2
+    assert gamma.is_contiguous() and beta.is_contiguous() and gamma.shape == beta.shape == (C,)
+    return B, C, T, stats.shape[1]
+
+
+def vqw2v_group_apply(x, stats, gamma, beta, *, relu=False, residual=None, residual_scale=1.0, log_compression=False):
+    """IN PLACE: x fp32 [B, C, T] <- gamma (x - mean) rstd + beta with the statistics of vqw2v_group_stats, then ReLU (relu), then
+    (x + residual[..., ::r_T // T][..., :T]) * residual_scale (residual fp32 [B, C, r_T]), then log(|x| + 1) (log_compression)"""
+    B, C, T, G = _affine(x, stats, gamma, beta)
+    r_T = rstep = 0
+    if residual is not None:
+        assert _chk(residual, F32).is_contiguous() and residual.shape[:2] == (B, C) and residual.shape[2] >= T
+        r_T = residual.shape[2]
+        rstep = r_T // T
+    _lib.call('alm_vqw2v_group_apply', x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _p(residual), B, C, T, G, r_T, rstep,
+              float(residual_scale), int(relu), int(log_compression), _st())
+    return x
+
+
+def vqw2v_group_apply_t(x, stats, gamma, beta):
+    """x fp32 [B, C, T] -> fp32 [B, T, C] = gamma (x - mean) rstd + beta, stored transposed (alm_vqw2v_group_apply_t)"""
+    B, C, T, G = _affine(x, stats, gamma, beta)
+    out = _new((B, T, C), dtype=F32, device=x.device)
+    _lib.call('alm_vqw2v_group_apply_t', x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), B, C, T, G, _st())
+    return out
+
+
+def vqw2v_conv0_stats(wave, w, stride, eps=1e-5):
+    """wave fp32 [B, Tin] (unit element stride), w fp32 [C, k] -> stats fp32 [B, 1, 2] = (mean, rstd) of nn.GroupNorm(1, C) over
+    conv1d(wave, w, stride), the activation never stored (alm_vqw2v_conv0_stats: the per-chunk partials of hubert_conv0_stats, merged per row)"""
+    _chk(wave, F32)
+    _chk(w, F32)
+    assert wave.dim() == 2 and w.dim() == 2 and w.is_contiguous()
+    wave, ld = _rows(wave)
+    B, Tin = wave.shape
+    C, k = w.shape
+    if Tin < k:
+        raise _lib.AlmError(f'the wave has {Tin} samples, fewer than the first conv kernel ({k})')
+    Tout = (Tin - k) // stride + 1
+    part = _new((B, C, _lib.query('alm_hubert_conv0_chunks', Tout), 2), dtype=F32, device=wave.device)
+    stats = _new((B, 1, 2), dtype=F32, device=wave.device)
+    _lib.call('alm_vqw2v_conv0_stats', wave.data_ptr(), ld, w.data_ptr(), part.data_ptr(), stats.data_ptr(), B, C, Tin, Tout, k, stride, float(eps), _st())
+    return stats
+
+
+def vqw2v_conv0_apply(wave, w, stats, gamma, beta, stride, log_compression=False):
+    """-> fp32 [B, C, Tout] = relu(GroupNorm(1, C)(conv1d(wave, w, stride))) with the statistics of vqw2v_conv0_stats (then log(. + 1))"""
+    _chk(wave, F32)
+    _chk(stats, F32)
+    wave, ld = _rows(wave)
+    B, Tin = wave.shape
+    C, k = w.shape
+    Tout = (Tin - k) // stride + 1
+    assert stats.shape == (B, 1, 2) and stats.is_contiguous() and w.is_contiguous() and gamma.is_contiguous() and beta.is_contiguous()
+    assert gamma.shape == beta.shape == (C,)
+    out = _new((B, C, Tout), dtype=F32, device=wave.device)
+    _lib.call('alm_vqw2v_conv0_apply', wave.data_ptr(), ld, w.data_ptr(), stats.data_ptr(), _chk(gamma, F32).data_ptr(), _chk(beta, F32).data_ptr(),
+              out.data_ptr(), B, C, Tin, Tout, k, stride, int(log_compression), _st())
+    return out
+
+
 # ---- T5 text encoder (csrc/t5.hip; t5_attn: csrc/dense_f32.hip): activations fp32 [C, N], N = B * T columns ----
 def t5_embed(ids, table):
     """ids int64 [B, T], table fp32 [vocab, D] -> fp32 [D, B * T] (alm_t5_embed).  An id outside the table is embedded as zeros and raises the

@@ -1260,3 +1260,12 @@ class SoundStream(nn.Module):
                     for sub in layer:
                         h = sub(h)
             return h
+
+
+# ---- the reference's two presets (soundstream.py:999-1023) ----
+def AudioLMSoundStream(strides=(2, 4, 5, 8), target_sample_hz=16000, rq_num_quantizers=12, **kwargs):
+    return SoundStream(strides=strides, target_sample_hz=target_sample_hz, rq_num_quantizers=rq_num_quantizers, **kwargs)
+
+
+def MusicLMSoundStream(strides=(3, 4, 5, 8), target_sample_hz=24000, rq_num_quantizers=12, **kwargs):
+    return SoundStream(strides=strides, target_sample_hz=target_sample_hz, rq_num_quantizers=rq_num_quantizers, **kwargs)

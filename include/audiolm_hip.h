@@ -522,6 +522,30 @@ int alm_layernorm_bct_split(const float* x, const float* gamma, const float* bet
  * softmax((scale q) . k) v per head, flash style (online softmax, no score matrix in memory).  dim_head == 64, else ALM_ERR_UNSUPPORTED. */
 int alm_mha_attn_fwd(const float* qkv, float* out, int B, int H, int T, int dim_head, float scale, void* stream);
 
+/* ---- FairseqVQWav2Vec (vq_wav2vec.py:19-81; csrc/vq_wav2vec.hip): fairseq's Wav2VecModel with the k-means quantizer (models/wav2vec/wav2vec.py
+ * ConvFeatureExtractionModel + KmeansVectorQuantizer, third-party, restated in tests/vq_wav2vec_restated.py).  fp32, [B][C][T]; the convs are
+ * alm_conv1d_valid, the code search alm_rvq_encode.  No atomics: every result is bitwise reproducible.
+ * _group_stats: nn.GroupNorm(G, C) statistics of x [B][C][T]: stats [B][G][2] = (mean, rstd) over each sample's contiguous (C / G) x T block, biased
+ *   variance; part [B][G][alm_vqw2v_group_chunks(C, T, G)][2] floats of workspace: (mean, M2) per chunk of 4096 elements, centred sums (never
+ *   E[x^2] - E[x]^2), merged by Chan's update in fp64 in a fixed order.
+ * _group_apply: in place, x = gamma[c] (x - mean) rstd + beta[c]; relu: max(., 0); residual [B][C][r_T] (or NULL): x = (x + residual[t * rstep])
+ *   * scale, needs (T - 1) rstep < r_T; logc: x = log(|x| + 1).  In that order (ConvFeatureExtractionModel.forward).
+ * _group_apply_t: out [B][T][C] = gamma (x - mean) rstd + beta, the transposed store the per-group code search reads with row stride C.
+ * _conv0_stats / _conv0_apply: layer 0 (Cin = 1) without storing the un-normalised activation, the arguments of alm_hubert_conv0_* with
+ *   GroupNorm(1, C): part [B][C][alm_hubert_conv0_chunks(Tout)][2] (the same partials), stats [B][2], out = relu(.) (logc: log(. + 1) after it).
+ * ALM_ERR_BAD_ARG when G does not divide C; ALM_ERR_UNSUPPORTED when C T (and with it an in-group index) does not fit 32 bits or B G > 65535;
+ * alm_vqw2v_group_chunks returns -1 for such a shape.  Sample and group offsets are 64-bit. */
+int alm_vqw2v_group_chunks(int C, int T, int G);
+int alm_vqw2v_group_stats(const float* x, float* part, float* stats, int B, int C, int T, int G, float eps, void* stream);
+int alm_vqw2v_group_apply(float* x, const float* stats, const float* gamma, const float* beta, const float* residual, int B, int C, int T, int G,
+                          int r_T, int rstep, float scale, int relu, int logc, void* stream);
+int alm_vqw2v_group_apply_t(const float* x, const float* stats, const float* gamma, const float* beta, float* out, int B, int C, int T, int G,
+                            void* stream);
+int alm_vqw2v_conv0_stats(const float* wave, long long ld_wave, const float* w, float* part, float* stats, int B, int C, long long Tin,
+                          long long Tout, int ksize, int stride, float eps, void* stream);
+int alm_vqw2v_conv0_apply(const float* wave, long long ld_wave, const float* w, const float* stats, const float* gamma, const float* beta,
+                          float* out, int B, int C, long long Tin, long long Tout, int ksize, int stride, int logc, void* stream);
+
 /* ---- T5 text encoder (csrc/t5.hip; _attn_fwd: csrc/dense_f32.hip): transformers T5Stack (encoder) as the reference's t5.py:68-110 calls it,
  * restated in tests/t5_restated.py.
  * fp32, inference only.  Activations are [C][N], N = B T columns (sample b = columns b T .. b T + T - 1); the bias-less Linear layers are

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X for the hot-path shapes (B=8 x N=2048 tokens, D=1024): every GEMM variant vs the vendor
 BLAS yardstick (torch.matmul; NOT part of the product), attention fwd/bwd, hyper-connection kernels.  Prints one line per case:
-name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty] [se_film] [fsq] [lfq] [gate_loop]"""
+name, ms, TFLOP/s or GB/s.   usage: python scripts/kbench.py [gemm] [attn] [hc] [misc] [t5] [convs_bwd] [local_attn_bwd] [rvq_train] [discr] [stft_discr] [mel_loss] [grad_penalty] [se_film] [fsq] [lfq] [gate_loop] [vqw2v]"""
 import os
 import sys
 import time
@@ -1288,6 +1288,57 @@ def bench_gate_loop():
         del ss
     for label, (t_tok, t_dec) in rows:
         print(f'default SoundStream, {B} x {n} samples, {label:22s}: tokenize {t_tok:8.2f} ms   decode {t_dec:8.2f} ms', flush=True)
+
+
+def bench_vqw2v():
+    """native FairseqVQWav2Vec.forward at the released size (8 conv layers of 512 channels, 2 groups of 320 codes), 8 x 30 s at 16 kHz, against the
+    plain-torch restatement (tests/vq_wav2vec_restated.py) in fp32 eager torch on the same GPU in the same process.  One event pair per forward,
+    median of 20 after 3 warm-up runs; then the same for each native stage."""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import vq_wav2vec_restated as VR
+    sd = VR.random_state_dict(1)
+    sd['vector_quantizer.embedding'] = torch.randn(320, 2, 256, generator=torch.Generator().manual_seed(2))
+    m = A.FairseqVQWav2Vec.from_state_dict(sd, target_sample_hz=16000).to(dev)
+    sdg = {k: v.to(dev) for k, v in sd.items()}
+    wave = torch.randn(8, 480000, device=dev) * 0.3
+
+    def median_ms(fn, iters=20, warm=3):
+        for _ in range(warm):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        return ts[len(ts) // 2], ts[0], ts[-1]
+    with torch.no_grad():
+        nat = median_ms(lambda: m(wave))
+        feat = median_ms(lambda: m.features(wave))
+        ze = m.features(wave)
+        asg = median_ms(lambda: m.assign(ze))
+        ref = median_ms(lambda: VR.assign(VR.features(sdg, wave), sdg['vector_quantizer.embedding']), iters=5, warm=1)
+        same = float((m(wave, flatten=False) == VR.assign(VR.features(sdg, wave), sdg['vector_quantizer.embedding'])).float().mean())
+    w0 = sd['feature_extractor.conv_layers.0.0.weight'].view(512, 10).to(dev)
+    g, b = sdg['feature_extractor.conv_layers.0.2.weight'], sdg['feature_extractor.conv_layers.0.2.bias']
+    st0 = ops.vqw2v_conv0_stats(wave, w0, 5)
+    x0 = ops.vqw2v_conv0_apply(wave, w0, st0, g, b, 5)
+    x1 = ops.conv1d_valid(x0, sdg['feature_extractor.conv_layers.1.0.weight'], stride=4)
+    st1 = ops.vqw2v_group_stats(x1, 1)
+    gb = lambda t: t.numel() * 4 / 1e6                             # noqa: E731
+    for name, fn, mb in (('conv0 stats', lambda: ops.vqw2v_conv0_stats(wave, w0, 5), gb(wave)),
+                         ('conv0 apply', lambda: ops.vqw2v_conv0_apply(wave, w0, st0, g, b, 5), gb(wave) + gb(x0)),
+                         ('conv layer 1 (512 -> 512, k 8, s 4)', lambda: ops.conv1d_valid(x0, sdg['feature_extractor.conv_layers.1.0.weight'], stride=4), gb(x0) + gb(x1)),
+                         ('group stats layer 1', lambda: ops.vqw2v_group_stats(x1, 1), gb(x1)),
+                         ('group apply layer 1 (in place)', lambda: ops.vqw2v_group_apply(x1, st1, g, b, relu=True), 2 * gb(x1))):
+        t = median_ms(fn)
+        print(f'  {name:38s} {t[0]:8.3f} ms (min {t[1]:.3f}, max {t[2]:.3f})  {mb / t[0]:7.0f} GB/s', flush=True)
+    print(f'vq-wav2vec released size 8 x 480000: native forward {nat[0]:.3f} ms (min {nat[1]:.3f}, max {nat[2]:.3f}; features {feat[0]:.3f}, assign {asg[0]:.3f})   '
+          f'eager torch fp32 {ref[0]:.3f} ms (min {ref[1]:.3f}, max {ref[2]:.3f})   native / eager {nat[0] / ref[0]:.2f}   ids equal on {100 * same:.2f} %')
 
 
 if __name__ == '__main__':
