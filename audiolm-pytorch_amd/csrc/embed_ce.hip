@@ -981,6 +981,7 @@ extern "C" int alm_scatter_rows_bf16(const void* in, long long ld_in, const int*
 extern "C" int alm_cross_entropy_fwd(const float* logits, long long ld, const long long* labels, float* loss_rows, float* lse, long long rows,
                                      int C, int ignore_index, void* stream) {
     if (rows <= 0) return 0;
+    if (!logits || !labels || !loss_rows || !lse || C < 1 || ld < C) return ALM_ERR_BAD_ARG;
     const int grid = (int)((rows + 3) / 4 < 8192 ? (rows + 3) / 4 : 8192);
     hipLaunchKernelGGL(ce_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, labels, loss_rows, lse, rows, C, ignore_index);
     ALM_LAUNCH_CHECK();
@@ -990,7 +991,7 @@ extern "C" int alm_cross_entropy_fwd(const float* logits, long long ld, const lo
 extern "C" int alm_cross_entropy_bwd(const float* logits, long long ld, const long long* labels, const float* lse, const float* gscale,
                                      void* dlogits, long long ldd, long long rows, int C, int Cpad, int ignore_index, void* stream) {
     if (rows <= 0) return 0;
-    if (Cpad < C || ldd < Cpad) return ALM_ERR_BAD_ARG;
+    if (!logits || !labels || !lse || !gscale || !dlogits || C < 1 || ld < C || Cpad < C || ldd < Cpad) return ALM_ERR_BAD_ARG;
     const int grid = (int)((rows + 3) / 4 < 8192 ? (rows + 3) / 4 : 8192);
     hipLaunchKernelGGL(ce_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, labels, lse, gscale, (bf16_t*)dlogits, ldd, rows,
                        C, Cpad, ignore_index);
@@ -999,6 +1000,7 @@ extern "C" int alm_cross_entropy_bwd(const float* logits, long long ld, const lo
 }
 
 extern "C" int alm_reduce_sum(const float* in, long long n, float* out, float scale, void* stream) {
+    if (!out || n < 0 || (n > 0 && !in)) return ALM_ERR_BAD_ARG;
     hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, in, n, out, scale);
     ALM_LAUNCH_CHECK();
     return 0;

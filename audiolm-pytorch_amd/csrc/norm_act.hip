@@ -453,7 +453,9 @@ extern "C" int alm_ln_partial_blocks(int rows) { return min((rows + 3) / 4, 512)
 extern "C" int alm_layernorm_fwd(const void* x, int x_is_bf16, long long ldx, const float* gamma, void* y, int y_is_f32, long long ldy, void* xcopy,
                                  long long ldc, float* mean, float* rstd, int rows, int D, void* stream) {
     if (rows <= 0) return 0;
-    if ((D & 3) || (ldx & 3) || (ldy & 3) || (xcopy && (ldc & 3))) return ALM_ERR_BAD_ARG;
+    if (!x || !gamma || !y || !mean || !rstd) return ALM_ERR_BAD_ARG;
+    if (D < 4 || (D & 3) || (ldx & 3) || (ldy & 3) || (xcopy && (ldc & 3))) return ALM_ERR_BAD_ARG;
+    if (ldx < D || ldy < D || (xcopy && ldc < D)) return ALM_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     int rc;
     if (y_is_f32)
@@ -472,7 +474,9 @@ extern "C" int alm_layernorm_bwd(const void* dy, int dy_is_f32, long long lddy, 
                                  const float* rstd, const float* gamma, const void* extra, long long lde, void* dx, int dx_is_bf16,
                                  long long lddx, float* dgamma_part, int rows, int D, void* stream) {
     if (rows <= 0) return 0;
-    if ((D & 3) || (ldx & 3) || (lddy & 3) || (lddx & 3) || (extra && (lde & 3))) return ALM_ERR_BAD_ARG;
+    if (!dy || !x || !mean || !rstd || !gamma || !dx) return ALM_ERR_BAD_ARG;
+    if (D < 4 || (D & 3) || (ldx & 3) || (lddy & 3) || (lddx & 3) || (extra && (lde & 3))) return ALM_ERR_BAD_ARG;
+    if (ldx < D || lddy < D || lddx < D || (extra && lde < D)) return ALM_ERR_BAD_ARG;
     const int grid = alm_ln_partial_blocks(rows);
     hipStream_t st = (hipStream_t)stream;
     int rc;
@@ -497,7 +501,7 @@ extern "C" int alm_layernorm_bwd(const void* dy, int dy_is_f32, long long lddy, 
 // saves the finish launch
 extern "C" int alm_colsum_chunks(int rows);
 extern "C" int alm_colsum_partial(const float* in, long long ld, int rows, int cols, float* ws, void* stream) {
-    if (cols <= 0 || rows <= 0 || !ws) return ALM_ERR_BAD_ARG;
+    if (cols <= 0 || rows <= 0 || !ws || !in || ld < cols) return ALM_ERR_BAD_ARG;
     const int chunks = alm_colsum_chunks(rows);
     const int rpc = (rows + chunks - 1) / chunks;
     hipLaunchKernelGGL(colsum_kernel<float>, dim3((cols + 63) / 64, chunks), dim3(256), 0, (hipStream_t)stream, in, ld, rows, cols, ws, 1.f, 0, rpc, 0);
@@ -511,6 +515,7 @@ extern "C" int alm_colsum_chunks(int rows) { return rows <= 128 ? 1 : min(16, (r
 extern "C" int alm_colsum(const void* in, int in_is_bf16, long long ld, int rows, int cols, float* out, float scale, int accumulate, float* ws,
                           void* stream) {
     if (cols <= 0) return 0;
+    if (!out || (rows > 0 && (!in || ld < cols))) return ALM_ERR_BAD_ARG;
     const int chunks = ws ? alm_colsum_chunks(rows) : 1;
     const int rpc = (rows + chunks - 1) / chunks;
     const int direct = chunks == 1;
@@ -531,7 +536,9 @@ extern "C" int alm_geglu_partial_blocks(int rows) { return min(rows, 1024); }
 extern "C" int alm_geglu_ln_fwd(const void* u, long long ldu, int gate_offset, const float* gamma, void* out, long long ldo, float* mean,
                                 float* rstd, int rows, int inner, int inner_pad, void* stream) {
     if (rows <= 0) return 0;
+    if (!u || !gamma || !out || !mean || !rstd) return ALM_ERR_BAD_ARG;
     if (inner <= 0 || inner_pad < inner || inner_pad > GE_MAX * 1024 || (inner_pad & 7) || (ldu & 7) || (gate_offset & 7)) return ALM_ERR_UNSUPPORTED;
+    if (gate_offset < inner_pad || ldu < (long long)gate_offset + inner_pad || ldo < inner_pad || (ldo & 3)) return ALM_ERR_BAD_ARG;
     hipLaunchKernelGGL(geglu_ln_fwd_kernel, dim3(min(rows, 2048)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)u, ldu, gate_offset, gamma,
                        (bf16_t*)out, ldo, mean, rstd, rows, inner, inner_pad);
     ALM_LAUNCH_CHECK();
@@ -543,7 +550,9 @@ extern "C" int alm_geglu_ln_bwd(const void* dhn, long long lddh, const void* u, 
                                 const float* mean, const float* rstd, void* du, float* dgamma_part, int rows, int inner, int inner_pad,
                                 void* stream) {
     if (rows <= 0) return 0;
+    if (!dhn || !u || !gamma || !mean || !rstd || !du) return ALM_ERR_BAD_ARG;
     if (inner <= 0 || inner_pad < inner || inner_pad > GE_MAX * 1024 || (inner_pad & 7) || (ldu & 7) || (gate_offset & 7)) return ALM_ERR_UNSUPPORTED;
+    if (gate_offset < inner_pad || ldu < (long long)gate_offset + inner_pad || lddh < inner_pad || (lddh & 3)) return ALM_ERR_BAD_ARG;
     hipLaunchKernelGGL(geglu_ln_bwd_kernel, dim3(alm_geglu_partial_blocks(rows)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dhn, lddh,
                        (const bf16_t*)u, ldu, gate_offset, gamma, mean, rstd, (bf16_t*)du, dgamma_part, rows, inner, inner_pad);
     ALM_LAUNCH_CHECK();
@@ -552,6 +561,7 @@ extern "C" int alm_geglu_ln_bwd(const void* dhn, long long lddh, const void* u, 
 
 extern "C" int alm_geglu_fwd(const float* x, float* y, long long rows, int inner, void* stream) {
     if (rows <= 0 || inner <= 0) return 0;
+    if (!x || !y) return ALM_ERR_BAD_ARG;
     const long long n = rows * inner;
     hipLaunchKernelGGL(geglu_fwd_kernel, dim3((unsigned)min((n + 255) / 256, (long long)8192)), dim3(256), 0, (hipStream_t)stream, x, y, rows, inner);
     ALM_LAUNCH_CHECK();
@@ -560,6 +570,7 @@ extern "C" int alm_geglu_fwd(const float* x, float* y, long long rows, int inner
 
 extern "C" int alm_geglu_bwd(const float* dy, const float* x, float* dx, long long rows, int inner, void* stream) {
     if (rows <= 0 || inner <= 0) return 0;
+    if (!dy || !x || !dx) return ALM_ERR_BAD_ARG;
     const long long n = rows * inner;
     hipLaunchKernelGGL(geglu_bwd_kernel, dim3((unsigned)min((n + 255) / 256, (long long)8192)), dim3(256), 0, (hipStream_t)stream, dy, x, dx, rows, inner);
     ALM_LAUNCH_CHECK();

@@ -128,6 +128,9 @@ typedef struct {
 int alm_pack_weights_multi(const AlmPackJob* jobs, int njobs, void* stream);
 
 /* ---- LayerNorm (gamma only, eps 1e-5): audiolm_pytorch.py:191-198 ---------------------------------------------------------- */
+/* rows <= 0 returns 0.  Otherwise, before any launch: ALM_ERR_BAD_ARG for a NULL x / gamma / y / mean / rstd / dy / dx, D < 4 or D % 4, a leading
+ * dimension that is no multiple of 4 or narrower than D (ldc / lde only with xcopy / extra); ALM_ERR_UNSUPPORTED for D > 2048 and for an fp32 dy with a
+ * bf16 x or dx.  alm_colsum / alm_colsum_partial: ALM_ERR_BAD_ARG for a NULL out / ws, and with rows > 0 a NULL in or ld < cols. */
 int alm_ln_partial_blocks(int rows);
 int alm_layernorm_fwd(const void* x, int x_is_bf16, long long ldx, const float* gamma, void* y, int y_is_f32, long long ldy, void* xcopy_bf16,
                       long long ldc, float* mean, float* rstd, int rows, int D, void* stream);   /* y bf16, or fp32 (final LayerNorm feeding the logit heads) */
@@ -142,7 +145,11 @@ int alm_colsum_chunks(int rows);
 int alm_colsum_partial(const float* in, long long ld, int rows, int cols, float* ws, void* stream);
 
 /* ---- GEGLU + inner LayerNorm: audiolm_pytorch.py:246-260 (gate = second half, exact-erf GELU, LN over int(dim*8/3)) -------- */
-/* standalone GEGLU module (audiolm_pytorch.py:246-249) on fp32 rows [rows][2 inner] -> [rows][inner]: y = x * gelu(gate), gate = the second half */
+/* standalone GEGLU module (audiolm_pytorch.py:246-249) on fp32 rows [rows][2 inner] -> [rows][inner]: y = x * gelu(gate), gate = the second half.
+ * alm_geglu_ln_*: u [rows][ldu] holds the x half at columns [0, inner_pad) and the gate half at [gate_offset, gate_offset + inner_pad); the pad columns
+ * [inner, inner_pad) are never counted and come out zero.  rows <= 0 returns 0.  Otherwise, before any launch: ALM_ERR_UNSUPPORTED for inner < 1,
+ * inner_pad < inner, inner_pad > 3072, inner_pad / ldu / gate_offset no multiple of 8; ALM_ERR_BAD_ARG for a NULL pointer (dgamma_part may be NULL),
+ * gate_offset < inner_pad, ldu < gate_offset + inner_pad, ldo / lddh < inner_pad or no multiple of 4. */
 int alm_geglu_fwd(const float* x, float* y, long long rows, int inner, void* stream);
 int alm_geglu_bwd(const float* dy, const float* x, float* dx, long long rows, int inner, void* stream);
 int alm_geglu_partial_blocks(int rows);
@@ -355,6 +362,8 @@ int alm_scatter_rows_bf16(const void* in, long long ld_in, const int* idx, void*
  * hi[r] / lo[r] = split(in[idx ? idx[r] : r]) for r < rows_out; source rows < 0 or >= rows_in give zero rows (ragged head groups, row padding). */
 int alm_gather_split_bf16(const float* in, long long ld_in, long long rows_in, const int* idx, void* hi, void* lo, long long ld_out,
                           long long rows_out, int D, void* stream);
+/* rows <= 0 returns 0; otherwise ALM_ERR_BAD_ARG before any launch for a NULL pointer, C < 1, ld < C, Cpad < C, ldd < Cpad.  A label equal to
+ * ignore_index, negative or >= C is ignored (loss 0, gradient row 0).  alm_reduce_sum: ALM_ERR_BAD_ARG for a NULL out, n < 0, or a NULL in with n > 0. */
 int alm_cross_entropy_fwd(const float* logits, long long ld, const long long* labels, float* loss_rows, float* lse, long long rows, int C,
                           int ignore_index, void* stream);
 int alm_cross_entropy_bwd(const float* logits, long long ld, const long long* labels, const float* lse, const float* gscale, void* dlogits_bf16,
