@@ -1285,6 +1285,9 @@ __global__ __launch_bounds__(256) void bias_grad_reduce_kernel(const float* __re
 static int check_attn(int B, int N, int H, long long ldq, long long ldk, long long ldv, long long ldo) {
     if (B <= 0 || N <= 0 || H <= 0 || H > 64) return ALM_ERR_UNSUPPORTED;
     if ((ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 3)) return ALM_ERR_BAD_ARG;
+    // a row holds its H * 64 (q, o) / 64 (k, v) columns: with a shorter pitch the rows >= N of the last Q tile lie INSIDE the DMA descriptor's num_records
+    // (it ends at (N - 1) * ld + width) and would be read from real memory instead of as zeros, and the o rows would overlap
+    if (ldq < (long long)H * DH || ldo < (long long)H * DH || ldk < DH || ldv < DH) return ALM_ERR_BAD_ARG;
     if ((long long)N * ldq * 2 >= 0x7fffffffLL || (long long)N * ldk * 2 >= 0x7fffffffLL || (long long)N * ldv * 2 >= 0x7fffffffLL) return ALM_ERR_UNSUPPORTED;
     // the tile DMA relies on the buffer bounds check for rows N .. N + 63 of the last tile: their 32-bit byte offsets must not wrap
     const long long ldmax = ldq > ldk ? (ldq > ldv ? ldq : ldv) : (ldk > ldv ? ldk : ldv);
@@ -1350,6 +1353,7 @@ static int attn_fwd_impl(const void* q, long long ldq, const void* k, long long 
     if (dim_head != DH) return ALM_ERR_UNSUPPORTED;
     int rc = check_attn(B, N, H, ldq, ldk, ldv, ldo);
     if (rc) return rc;
+    if (!q || !k || !v || !o || !lse) return ALM_ERR_BAD_ARG;
     if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)o & 7)) return ALM_ERR_BAD_ARG;
     AttnParams p{};
     p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.mask = mask; p.o = (bf16_t*)o; p.lse = lse;
@@ -1386,7 +1390,12 @@ static int attn_bwd_impl(const void* q, long long ldq, const void* k, long long 
     if (dropout_p < 0.f || dropout_p >= 1.f) return ALM_ERR_BAD_ARG;
     int rc = check_attn(B, N, H, ldq, ldk, ldv, ldo);
     if (rc) return rc;
+    if (!q || !k || !v || !o || !lse || !dout || !dq || !dk || !dv || !delta) return ALM_ERR_BAD_ARG;
     if ((lddo & 7) || (lddq & 3) || (long long)N * lddo * 2 >= 0x7fffffffLL) return ALM_ERR_BAD_ARG;
+    // dO tile DMA / dq rows: as ldq / ldo in check_attn.  dk / dv rows are 64 fp32 columns, written and read back (alm_kv_grad_pack) one float at a time, as
+    // is lse: no alignment beyond the element's; partial set g starts part_stride floats after set g - 1 and must not overlap it
+    if (lddo < (long long)H * DH || lddq < (long long)H * DH || lddk < DH) return ALM_ERR_BAD_ARG;
+    if (alm_mqa_bwd_parts(B, N, H) > 1 && part_stride < (long long)B * N * lddk) return ALM_ERR_BAD_ARG;
     if ((long long)(N + 64) * lddo * 2 >= 0xffffffffLL) return ALM_ERR_UNSUPPORTED;          // dO tile DMA: see check_attn
     rc = check_bias(ba, true);
     if (rc) return rc;

@@ -1017,7 +1017,9 @@ extern "C" int alm_value_residual_mix(const void* v, long long ldv, const void* 
 
 extern "C" int alm_kv_grad_pack(const float* dk, const float* dv, long long ld, int nparts, long long part_stride, float* acc_v0, void* dkv,
                                 long long ldo, long long rows, int dim_head, int mode, void* stream) {
-    if (mode < 0 || mode > 2 || (mode && !acc_v0) || nparts < 1) return ALM_ERR_BAD_ARG;
+    if (mode < 0 || mode > 2 || (mode && !acc_v0) || nparts < 1 || rows < 0) return ALM_ERR_BAD_ARG;
+    if (rows == 0) return 0;
+    if (!dk || !dv || !dkv || dim_head < 1 || ld < dim_head || ldo < 2 * (long long)dim_head || (nparts > 1 && part_stride < rows * ld)) return ALM_ERR_BAD_ARG;
     hipLaunchKernelGGL(kv_grad_pack_kernel, dim3(grid_for(rows * dim_head)), dim3(256), 0, (hipStream_t)stream, dk, dv, ld, nparts, part_stride,
                        acc_v0, (bf16_t*)dkv, ldo, rows, dim_head, mode);
     ALM_LAUNCH_CHECK();

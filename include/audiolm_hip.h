@@ -167,7 +167,16 @@ int alm_geglu_ln_bwd(const void* dhn_bf16, long long lddh, const void* u_bf16, l
  * (b, h, i, j) is kept iff hash(seed, b, h, i * N + j) >= dropout_p * 2^32 (a stateless 32-bit finaliser, the same in forward, dQ and dK/dV) and
  * scaled by 1 / (1 - dropout_p); 0 = off (the default path, no cost).  Pass the forward's (dropout_p, seed, seed_dev) to the backward.
  * seed_dev (device uint64 | NULL): when given, the stream is seed + *seed_dev with the counter read when the kernel RUNS -- a hipGraph replay then
- * draws a new mask each time (a by-value seed is baked into the captured launch); the caller advances the counter on the device between steps. */
+ * draws a new mask each time (a by-value seed is baked into the captured launch); the caller advances the counter on the device between steps.
+ * A query without a visible key (every key j <= i masked) gets o = 0 and lse = -inf and contributes nothing to dq, dk, dv or the table gradient; a
+ * masked key gets dk = dv = 0 and its K / V rows never reach an output.
+ * Refused before any launch.  ALM_ERR_UNSUPPORTED: B, N, H < 1, H > 64, dim_head != 64, N rows of pitch ldq / ldk / ldv of 2^31 bytes or more, N + 64
+ * rows of any pitch of 2^32 bytes or more (the tile DMA's 32-bit offsets would wrap).  ALM_ERR_BAD_ARG: N * lddo * 2 >= 2^31 (backward);
+ * dropout_p outside [0, 1); a NULL q / k / v / o / lse (backward: also dout / dq / dk / dv / delta); ldq, lddo < H*64 or no multiple
+ * of 8 (16-byte tile DMA and fragment loads), ldk, ldv < 64 or no multiple of 8 (the same), ldo, lddq < H*64 or no multiple of 4 (8-byte stores of o and
+ * dq), lddk < 64, part_stride < B*N*lddk when alm_mqa_bwd_parts(B,N,H) > 1; q, k, v, dout not 16-byte aligned, dq not 8-byte aligned, o not 8-byte aligned
+ * in the forward (the backward only READS o, with global loads that take any element-aligned address: its base is not checked there).
+ * dk / dv / lse / delta are read and written one float at a time: they need no alignment beyond a float's, and lddk, part_stride need no multiple. */
 int alm_mqa_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, const unsigned char* mask,
                      void* o, long long ldo, float* lse, int B, int N, int H, int dim_head, float scale, float dropout_p,
                      unsigned long long seed, const void* seed_dev, void* stream);
@@ -237,6 +246,9 @@ int alm_xattn_delta(const void* o_bf16, long long ldo, const void* dout_bf16, lo
 /* value residual, audiolm_pytorch.py:353-358 / :534-535 */
 int alm_value_residual_mix(const void* v, long long ldv, const void* v0, long long ldv0, void* out, long long ldo, long long rows,
                            int dim_head, void* stream);
+/* dkv_bf16 [rows][ldo] = (sum of the nparts fp32 partial sets of dk | the same of dv) rounded once; mode 0: no value residual, 1: dv is halved and added to
+ * acc_v0 [rows][dim_head], 2: acc_v0 is added to dv.  rows == 0 returns 0.  ALM_ERR_BAD_ARG before any launch: mode outside 0..2, mode != 0 without acc_v0,
+ * nparts < 1, rows < 0, a NULL dk / dv / dkv_bf16, dim_head < 1, ld < dim_head, ldo < 2 dim_head, part_stride < rows * ld with nparts > 1.  Scalar accesses only. */
 int alm_kv_grad_pack(const float* dk, const float* dv, long long ld, int nparts, long long part_stride, float* acc_v0, void* dkv_bf16,
                      long long ldo, long long rows, int dim_head, int mode, void* stream);
 
