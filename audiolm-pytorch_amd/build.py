@@ -16,6 +16,7 @@ CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'build')                       # git-ignored (objects + per-object digests)
 LIB = os.path.join(HERE, 'libaudiolm_hip.so')
 STAMP = os.path.join(HERE, '.libaudiolm_hip.stamp')
+HEADER = os.path.join(HERE, '..', 'include', 'audiolm_hip.h')      # the C ABI: digested here, parsed into the ctypes binding by _lib.py
 SOURCES = ['gemm.hip', 'norm_act.hip', 'attention.hip', 'hyper.hip', 'embed_ce.hip', 'codec.hip', 'relpos.hip', 'optim.hip', 'decode.hip',
            'xattn.hip', 'local_attn.hip', 'launchlist.hip', 'resample.hip', 'dense_f32.hip', 'hubert.hip', 't5.hip',
            'encodec.hip', 'codec_bwd.hip', 'local_attn_bwd.hip', 'rvq_train.hip', 'discr.hip', 'stft_discr.hip', 'mel_loss.hip',
@@ -25,7 +26,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-val
 
 def _headers() -> bytes:
     h = hashlib.sha256()
-    files = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(('.hpp', '.h'))] + [os.path.join(HERE, '..', 'include', 'audiolm_hip.h')]
+    files = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(('.hpp', '.h'))] + [HEADER]
     for f in files:
         with open(f, 'rb') as fh:
             h.update(os.path.basename(f).encode() + b'\0' + fh.read())

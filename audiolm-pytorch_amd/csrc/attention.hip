@@ -38,7 +38,6 @@
 
 #include "common.hpp"
 #include "launch.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

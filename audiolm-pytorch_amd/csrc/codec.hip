@@ -24,7 +24,6 @@
 #include "common.hpp"
 #include "launch.hpp"
 #include "conv1d.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

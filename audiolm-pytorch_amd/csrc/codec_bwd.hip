@@ -23,7 +23,6 @@
 //           time while the MFMA wants the channel on the lane axis: the tiles go through LDS (coalesced row loads in, transposed reads out).
 //   Cin = 1 / Cout = 1 (first encoder conv, last decoder conv) run the same kernels on a zero-padded 32-channel tile.
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

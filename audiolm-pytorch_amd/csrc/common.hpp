@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/audiolm_hip.h"      // every translation unit compiles against the C ABI it defines (prototypes, structs, ALM_ERR_*)
+
 typedef uint16_t bf16_t;                                             // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -11,10 +13,6 @@ typedef __attribute__((ext_vector_type(8))) short bf16x8;            // one MFMA
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
 
 #define ALM_WAVE 64
-
-// error codes returned through the C ABI (0 == hipSuccess)
-#define ALM_ERR_BAD_ARG 10001
-#define ALM_ERR_UNSUPPORTED 10002
 
 #define ALM_LAUNCH_CHECK()                       \
     do {                                         \

@@ -10,7 +10,6 @@
 // online softmax with wave-uniform statistics, then lane = head dim accumulates sum_j p_j v[j][d] with the probabilities passed through
 // LDS.  HBM-bound and tiny (n * 256 B per sequence and layer): the point is that a sampling step costs O(n), not a full forward.
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

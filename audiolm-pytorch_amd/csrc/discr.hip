@@ -21,7 +21,6 @@
 // Gradient penalty (soundstream.py:70-83) weight / R sum_r (|G_r| - center)^2 of G [R][n]: the rows' sums of squares the same way (per-block spans of a
 // row, partials added in index order), the R norms kept for the elementwise backward.
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

@@ -7,7 +7,6 @@
 //   * value-residual mixing v <- (v + v_layer0) / 2 (:357-358) and the matching gradient fan-in.
 #include "common.hpp"
 #include "launch.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

@@ -16,7 +16,6 @@
 //                       rows).  c lives in a [L][B][H] buffer that only the owning wave touches.
 #include "common.hpp"
 #include "conv1d.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

@@ -22,7 +22,6 @@
 //   backward: dx = g gamma; dgamma[c] = sum_r g x, dbeta[c] = sum_r g as per-row-chunk partials in the workspace, summed in chunk order by the
 //   second launch, which writes dW [2 C][2] = (dgamma | dbeta) (x) cond and db = (dgamma | dbeta).
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

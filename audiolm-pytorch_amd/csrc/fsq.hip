@@ -20,7 +20,6 @@
 // thread (r, j) of the first 128 runs dimension j of row r in registers and the layer's index is a 3-step shuffle sum over the 8 lanes of a row.
 // backward: dz = g_z * sum_{q <= k} (half_l / half_w) (1 - t_q^2), the chain recomputed from the saved z.
 #include "proj_quant.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

@@ -16,7 +16,6 @@
 // reads h from a forward scan in `h only` mode); then the k = 1 conv's input / weight gradients (alm_conv1d_dgrad / alm_conv1d_wgrad), then
 // alm_gate_loop_norm_bwd: dx = r gamma dxn - x (r^3 / C) sum_k dxn_k gamma_k x_k + 2 g, dgamma from per-block partials added in block order.
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

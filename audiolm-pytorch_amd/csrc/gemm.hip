@@ -32,7 +32,6 @@
 #include "common.hpp"
 #include "launch.hpp"
 #include "gemm_plan.hpp"
-#include "../../include/audiolm_hip.h"
 
 // Cache policy of the operand DMA (`buffer_load ... lds` aux immediate: 1 = sc0, 2 = nt, 16 = sc1).  0 in the product build; scripts/build_variant.sh
 // builds measurement libraries with -DALM_GEMM_AUX_A=2 / -DALM_GEMM_AUX_B=2 (one operand streamed non-temporally past the L2: round 6, DESIGN labbook)

@@ -19,7 +19,6 @@
 #include <type_traits>
 
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 // A/B switch of the backward kernel's per-stream element loop (round 4): 1 = the token's per-stream scalars travel through a
 // per-wave LDS record as broadcast splat pairs + folded weights (24 % fewer VALU instructions, but 256 VGPRs + scratch spills whose reloads drain the

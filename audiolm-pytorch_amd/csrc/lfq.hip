@@ -27,7 +27,6 @@
 // [Q][M][d]; (2) lfq_bwd_kernel: proj_bwd with dz = (k + 1) g_z + the layers' loss gradients in layer order; (3) the chunk-order reduction of the
 // parameter gradients.
 #include "proj_quant.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

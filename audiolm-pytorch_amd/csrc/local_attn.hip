@@ -12,7 +12,6 @@
 // the lanes of a wave read consecutive slots) -- not an MFMA tiling.
 #include "common.hpp"
 #include "launch.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

@@ -15,7 +15,6 @@
 //   * GEGLU backward with the forward's erf GELU and its exact derivative.
 #include "common.hpp"
 #include "launch.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

@@ -18,7 +18,6 @@
 //                     torch's conventions: sign(0) = 0, nothing through an inactive clamp, nothing where l2 = 0 (each an exact 0, never 0 * inf).
 //                     Then dP = fb dMel (M = F, N = Bh T, K = n_mels) whose epilogue writes dX = 2 X dP; alm_stft_bwd takes dX to the wave.
 #include "gemm64.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

@@ -6,7 +6,6 @@
 // One wave (64 lanes) owns one LayerNorm row of <= 1024 features: 16-B coalesced loads, the row stays in registers,
 // reductions are wave-64 shuffles (no LDS, no block barrier).  The 2730-wide GEGLU row is owned by a 256-thread block.
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

@@ -13,7 +13,6 @@
 // the stream (a small H2D copy is not guaranteed to be asynchronous on every box): the suspected cause of the +1.9 ms "slow mode" of the
 // `with_optimizer` leg seen on some boxes and not on others (profiles/README.md).  The chunk tables depend on shapes only and stay on the device.
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

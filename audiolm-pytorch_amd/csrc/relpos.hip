@@ -9,7 +9,6 @@
 // The d x d layers are plain contractions and run on the MFMA GEMMs (gemm.hip) from the host mirror; this file holds the thin first layer
 // (1 or 2 inputs), the thin last layer (heads outputs), SiLU and their backward passes.  All fp32 except the bf16 GEMM operands.
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

@@ -19,7 +19,6 @@
 //       All three go through rvq_row_y, written with explicit roundings (no contraction freedom), so the backward's and the expiry's recomputed
 //       residual chain is bit-identical to the forward's.
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 #pragma clang fp contract(off)           // only the fmas that are written out: rvq_row_y must give the same bits in every kernel that inlines it
 

@@ -19,7 +19,6 @@
 // Second order (the double backward of the gradient penalty): the backward passes of ModReLU and |z| as functions of (g, z, b), differentiated once
 // more against the cotangents (v, beta) of (dz, db) -- elementwise again, the scalar d/db reduced like db.
 #include "gemm64.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

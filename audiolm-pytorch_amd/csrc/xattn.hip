@@ -15,7 +15,6 @@
 //     and the causal rule "key e visible to query n iff e <= n + causal_off" (causal_off = Me - N; INT_MAX: not causal) -- O(N^2) memory like
 //     the reference's math path; the structured biases of the model family never take it (attention.hip indexes their table in place).
 #include "common.hpp"
-#include "../../include/audiolm_hip.h"
 
 namespace {
 

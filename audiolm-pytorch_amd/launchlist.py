@@ -32,8 +32,8 @@ ENABLED = os.environ.get('ALM_LAUNCH_LIST', '1') != '0'
 MAX_ARENA_BYTES = int(float(os.environ.get('ALM_LAUNCH_LIST_MAX_GB', '24')) * (1 << 30))    # per pass; larger steps keep the eager path (frees as it goes)
 MAX_PLANS = max(1, int(os.environ.get('ALM_LAUNCH_LIST_MAX_PLANS', '64')))                   # recorded (configuration, shape) keys kept; least recently used dropped
 ALIGN = 256
-LITERAL, STREAM, HOST_PTRS, HOST_INTS = 0, 0xFFFF, 0xFFFE, 0xFFFD
-_P, _I, _L, _F, _U = _lib._P, _lib._I, _lib._L, _lib._F, _lib._U
+LITERAL, STREAM, HOST_PTRS, HOST_INTS = (_lib.CONSTANTS['ALM_LIST_' + n] for n in ('LITERAL', 'STREAM', 'HOST_PTRS', 'HOST_INTS'))
+_P, _F = _lib._P, _lib._F
 _M64 = (1 << 64) - 1
 
 STATS = dict(sized=0, recorded=0, replayed=0, refused=0)         # counters (tests / bench report them)

@@ -1978,7 +1978,7 @@ def lstm_seq(xproj, w_ih, w_hh, bias, *, skip=None, out_bct=False):
 
 # ---- wave discriminators of SoundStream training (csrc/discr.hip), fp32, no atomics
 
-LOSS_HINGE_DISCR, LOSS_HINGE_GEN, LOSS_L1, LOSS_MSE = 0, 1, 2, 3
+LOSS_HINGE_DISCR, LOSS_HINGE_GEN, LOSS_L1, LOSS_MSE = (_lib.CONSTANTS['ALM_LOSS_' + n] for n in ('HINGE_DISCR', 'HINGE_GEN', 'L1', 'MSE'))
 
 
 def gconv1d_out_len(Tin, ksize, stride, padding):
@@ -2118,7 +2118,7 @@ def grad_penalty_bwd(G, norms, gout, weight=10., center=0.):
 
 # ---- ComplexSTFTDiscriminator of SoundStream training (csrc/stft_discr.hip), fp32, no atomics.  Complex tensors travel as fp32 [..., 2] (re, im) pairs.
 
-LOSS_L1_COMPLEX = 4
+LOSS_L1_COMPLEX = _lib.CONSTANTS['ALM_LOSS_L1_COMPLEX']
 _STFT_BASIS = {}
 
 

@@ -10,14 +10,11 @@ import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+from audiolm_pytorch_amd._lib import AlmTnJob  # noqa: E402  (with ALM_LIB_PATH set the package loads that library: nothing is built)
 MN = (1, 64, 127, 128, 129, 255, 256, 257, 300, 512, 1024, 1025, 2730, 2736, 5472, 8192, 16384, 16392, 16448)
 KS = (8, 64, 200, 256, 1024, 2736, 4096, 16384, 131072)
 NB = (1, 2, 3, 6, 12, 24)
-
-
-class AlmTnJob(ctypes.Structure):
-    _fields_ = [('At', ctypes.c_void_p), ('Bt', ctypes.c_void_p), ('C', ctypes.c_void_p)] + [(n, ctypes.c_int) for n in ('M', 'N', 'K', 'nb1', 'nb2', 'accumulate')] + \
-               [('alpha', ctypes.c_float), ('reserved', ctypes.c_int)] + [(n, ctypes.c_longlong) for n in ('lda', 'ldb', 'ldc', 'sA1', 'sA2', 'sB1', 'sB2', 'sC1', 'sC2')]
 
 
 def job_lists():
